@@ -10,6 +10,16 @@ rank; groups spanning ranks add the partial all-gather over RCCL
 (opentsdb_amd/dist.py).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it generates
+the batch, warms up, times the K steps and prints the result line.
+--dump-outputs DIR then writes what the last timed step computed (the arrays
+a caller of the timed path receives) as DIR/<name>.npy.  --full adds every
+secondary measurement: the profiled pass behind the per-stage and
+per-kernel roofline figures, the CPU baseline, the named / p999 queries, the
+PCIe-inclusive rate and the compacted-cell figures (each with its --no-*
+switch).
 
 With --gpus N > 1 outside a torch.distributed launch, this process starts
 the N ranks itself (torch.distributed.run on 127.0.0.1, one rank per GPU)
@@ -42,6 +52,13 @@ def parse():
     ap.add_argument("--config", default="C2")
     ap.add_argument("--series", type=int, default=0,
                     help="series per GPU (default: the config's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result arrays as "
+                         "DIR/<name>.npy (float64 / float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: per-stage "
+                         "kernel times, CPU baseline, named / p999 query, "
+                         "PCIe-inclusive and compacted-cell figures")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-decode", action="store_true",
@@ -54,7 +71,10 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / collective rehearsal without the HIP "
                          "engine (CPU tests): times a gloo all-reduce")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -470,6 +490,69 @@ def cpu_baseline(config, target_s):
     return out
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # every .npy of one dump together (< 64 MB)
+
+
+def dump_outputs(out_dir, offsets, ts, val, is_int):
+    """--dump-outputs: the result a caller of the timed path receives, as
+    float64 / float32 .npy files.  offsets[g] .. offsets[g + 1] are group g's
+    output points; ts / val / is_int are torch tensors (any device) or numpy
+    arrays holding at least offsets[-1] points.  `values` are the points'
+    values as doubles (longs converted, like DataPoints.values()).
+
+    A result over the byte budget is written as a fixed sample: the same
+    `sample_index` (positions in the flat point arrays, seed 0) for the same
+    output size, so two builds are compared point for point."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    offsets = np.asarray(offsets, np.int64)
+    n = int(offsets[-1])
+    per_point = 8 + 8 + 4 + 8  # timestamps, values, is_int, sample_index
+    keep = max(0, (DUMP_BUDGET_BYTES - 8 * len(offsets)) // per_point)
+    idx = None
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+
+    def pick(a):
+        if isinstance(a, np.ndarray):
+            return a[:n] if idx is None else a[idx]
+        if idx is None:
+            return a[:n].cpu().numpy()
+        import torch
+        return a[torch.from_numpy(idx).to(a.device)].cpu().numpy()
+
+    bits = np.ascontiguousarray(pick(val), np.int64)
+    ints = pick(is_int).astype(bool)
+    values = bits.view(np.float64).copy()
+    values[ints] = bits[ints].astype(np.float64)
+    arrays = {"group_offsets": offsets.astype(np.float64),
+              "timestamps": pick(ts).astype(np.float64),
+              "values": values,
+              "is_int": ints.astype(np.float32)}
+    if idx is not None:
+        arrays["sample_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def dump_sharded(out_dir, result):
+    """dump_outputs for a ShardedResult / selection result: the groups this
+    rank holds, concatenated in global group order (`group_ids`)."""
+    import numpy as np
+    groups = result.host_groups()
+    ids = sorted(groups)
+    offsets = np.zeros(len(ids) + 1, np.int64)
+    np.cumsum([len(groups[g][0]) for g in ids], out=offsets[1:])
+
+    def cat(k, dtype):
+        return (np.concatenate([groups[g][k] for g in ids]) if ids
+                else np.zeros(0, dtype))
+    dump_outputs(out_dir, offsets, cat(0, np.int64), cat(1, np.int64),
+                 cat(2, np.uint8))
+    np.save(os.path.join(out_dir, "group_ids.npy"),
+            np.asarray(ids, np.float64))
+
+
 def dry_run(args, world, rank):
     """Launcher rehearsal for CPU tests: the same process-group setup,
     barrier-bracketed timing and max-over-ranks reduction, with a gloo
@@ -601,14 +684,24 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
 
-    read = stage_reader(eng)
-    eng.lib.otsdb_prof_enable(eng.ctx, 1)
-    read()  # reset
-    for _ in range(max(1, min(args.steps, 10))):
-        step()
-    torch.cuda.synchronize()
-    stage_ms = read()
-    eng.lib.otsdb_prof_enable(eng.ctx, 0)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result, before anything else runs
+        if sharded:
+            dump_sharded(args.dump_outputs, last[0])
+        else:
+            dump_outputs(args.dump_outputs, res.offsets.cpu().numpy(),
+                         res.ts, res.val, res.is_int)
+
+    stage_ms = None
+    if args.full:
+        read = stage_reader(eng)
+        eng.lib.otsdb_prof_enable(eng.ctx, 1)
+        read()  # reset
+        for _ in range(max(1, min(args.steps, 10))):
+            step()
+        torch.cuda.synchronize()
+        stage_ms = read()
+        eng.lib.otsdb_prof_enable(eng.ctx, 0)
 
     sel_counts = None
     if sharded and cfg["agg"] in ("p99", "p999", "median"):
@@ -637,7 +730,10 @@ def main():
     # pipeline (every stage: prep, downsample, transform, group / selection,
     # compact), with the downsample stage alone beside it
     row_path = bool(cfg["rate"]) or cfg["agg"] in ("p99", "p999", "median")
-    kb_s = (sum(stage_ms[:5]) if row_path else stage_ms[0]) / 1e3
+    # (the kernels' own HIP-event times come from --full's profiled pass)
+    kb_s = 0.0
+    if stage_ms:
+        kb_s = (sum(stage_ms[:5]) if row_path else stage_ms[0]) / 1e3
     kernel_achieved = (BYTES_PER_POINT * n_points / kb_s / 1e9
                        if kb_s > 0 else None)
     # the headline fraction: algorithmic bytes over the driver-timed step
@@ -651,7 +747,7 @@ def main():
               "pipeline: k_prep + k_bucketize_k + k_keys_transpose + "
               "k_seg_select + k_compact")
     ds_stage = None
-    if row_path and stage_ms[0] > 0:
+    if row_path and stage_ms and stage_ms[0] > 0:
         ds_stage = {"kernel": "k_bucketize_k", "ms": stage_ms[0],
                     "frac": BYTES_PER_POINT * n_points / (stage_ms[0] / 1e3)
                     / 1e9 / HBM_PEAK_GBS}
@@ -666,7 +762,7 @@ def main():
             traffic = tinfo["step"] or tinfo["dominant_kernel"]
 
     extra = {}
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_cpu_baseline:
             extra["cpu_baseline"] = cpu_baseline(args.config, args.cpu_seconds)
         if not args.no_extra and args.config == "C2":
@@ -677,7 +773,8 @@ def main():
             extra["pcie_inclusive"] = pcie_figure(eng, args.config)
 
     n_groups, n_buckets = db.n_groups, int(sz.n_buckets)
-    if world == 1 and not args.no_decode and args.config == "C2":
+    if (args.full and world == 1 and not args.no_decode
+            and args.config == "C2"):
         del db, res
         torch.cuda.empty_cache()
         extra["decode"] = decode_figure(eng, args.config, n_series)
@@ -710,10 +807,8 @@ def main():
                     world, (" + %s exchange of shared groups" % (
                         "RCCL" if backend == "nccl" else backend))
                     if sharded else ""),
-                "stage_ms": {"downsample": stage_ms[0],
-                             "transform": stage_ms[1],
-                             "group": stage_ms[2], "prep": stage_ms[3],
-                             "compact": stage_ms[4]},
+                "stage_ms": dict(zip(STAGES[:5], stage_ms)) if stage_ms
+                else None,
                 "generate_s": t_gen,
                 "sel_protocol": sel_counts,
             },
@@ -728,7 +823,7 @@ def main():
                 "traffic": traffic,
                 "traffic_pmc": tinfo,
                 "algorithmic_bytes_per_launch": BYTES_PER_POINT * n_points,
-                "kernel_ms": kb_s * 1e3,
+                "kernel_ms": kb_s * 1e3 if stage_ms else None,
                 "kernel_achieved": kernel_achieved,
                 "kernel_frac": (kernel_achieved / HBM_PEAK_GBS
                                 if kernel_achieved else None),

@@ -12,7 +12,7 @@ for c in ${CONFIGS:-C2}; do
     if [ "$v" = prod ]; then unset OTSDB_LIB; else export OTSDB_LIB=$PWD/opentsdb_amd/_build/var_$v/libotsdb_agg.so; fi
     if [ "$c" = named ]; then cfg="--config C2 --named-query"; else cfg="--config $c"; fi
     log=gpurun_out/r6_cfg/${c}_${v}_$r.log
-    timeout -k 10 300 python3 -u bench.py $cfg --steps ${STEPS:-10} --warmup 3 \
+    timeout -k 10 300 python3 -u bench.py $cfg --steps ${STEPS:-10} --warmup 3 --full \
       --no-cpu-baseline --no-extra --no-decode > $log 2>&1 || { tail -20 $log; exit 1; }
     tail -1 $log | python3 -c "
 import json,sys

@@ -29,10 +29,11 @@ fi
 NO_PROF=1 STEPS=20 CPU_S=${CPU_S:-10} bash scripts/gpu_bench_all.sh || exit $?
 CONFIGS="C1 C2 C3 C4 C5" bash scripts/gpu_kernel_stats.sh > gpurun_out/ks_all.log 2>&1 || { tail -5 gpurun_out/ks_all.log; exit 1; }
 echo "kernel stats ok"
-OTSDB_BENCH_SHARDED=1 timeout -k 10 300 python3 -u bench.py --config C5 --steps 20 \
+OTSDB_BENCH_SHARDED=1 timeout -k 10 300 python3 -u bench.py --config C5 --steps 20 --full \
   --no-cpu-baseline --no-extra > gpurun_out/bench_C5_sharded.log 2>&1 || exit $?
 tail -1 gpurun_out/bench_C5_sharded.log
 OTSDB_BENCH_SHARDED=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
   -d gpurun_out/ks_C5_sharded -o ks -- python3 -u bench.py --config C5 --steps 5 \
+  --full \
   --warmup 2 --no-cpu-baseline --no-extra --no-decode > gpurun_out/ks_C5_sharded.log 2>&1 || exit $?
 echo "sharded C5 ok"

@@ -13,7 +13,7 @@ tail -5 gpurun_out/pytest_gpu.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 180 python -u __graft_entry__.py smoke > gpurun_out/smoke.log 2>&1 || exit $?
 tail -2 gpurun_out/smoke.log
-timeout -k 10 300 python -u bench.py --series ${BENCH_SERIES:-20000} --steps 10 \
+timeout -k 10 300 python -u bench.py --series ${BENCH_SERIES:-20000} --steps 10 --full \
   --cpu-seconds 3 > gpurun_out/bench_small.log 2>&1 || exit $?
 tail -1 gpurun_out/bench_small.log
 exit $rc
