@@ -215,3 +215,34 @@ def test_comparator_sees_perturbed_fill_in_results():
             blind += int((1e-9 * np.abs(v[sel]) <= tol).sum())
     assert n > 20000, n
     assert blind <= n // 1000, (blind, n)
+
+
+@pytest.mark.parametrize("grouping", ["a", "b"])
+@pytest.mark.parametrize("kind", ["signed", "bigint"])
+def test_contribution_floors_are_bounded_on_edge_values(kind, grouping):
+    """test_contribution_floors_are_finite_and_bounded's bound on the edges
+    of the value domain (doubles of both signs over 10^+-150, longs over the
+    whole 64-bit range; tests/test_gpu_value_domain.py's batches and its
+    whole query matrix): every floor is finite and at most 2e-12 x the sum
+    over the group's members of the largest scale of the member's own view
+    stream."""
+    from tests.test_gpu_parity import _member_scales, _spec
+    from tests.value_domain import WINDOWS, edge_batch, matrix
+    b = edge_batch(kind, grouping)
+    s, e = WINDOWS[0]
+    n = 0
+    cache = {}  # the members' view streams do not depend on the aggregator
+    for agg, ds, fill in matrix():
+        spec = _spec(agg, ds, fill, s, e)
+        ref = pyoracle.group_by(spec, b)
+        views = cache.get((ds, fill))
+        if views is None:
+            views = cache[ds, fill] = _member_scales(spec, b)
+        fl = contribution_floor(spec, b, ref, views)
+        for g, (f, gv) in enumerate(zip(fl, views)):
+            assert np.isfinite(f).all(), (agg, ds, fill)
+            bound = 2e-12 * sum(float(sc.max()) for _, _, sc in gv if len(sc))
+            assert (f <= bound).all(), "%s:%s-%s/g%d: floor %g > %g" % (
+                agg, ds, fill, g, f.max(), bound)
+            n += len(f)
+    assert n > 100

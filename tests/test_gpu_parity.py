@@ -551,8 +551,8 @@ def test_percentiles_large_groups(engine, n_series, kind):
 def test_percentiles_fill_several_large_groups(engine):
     """Fill-mode percentiles with every group large: the keys transpose
     applies the FillingDownsampler fill and counts the non-NaN keys per
-    (bucket, 64-member tile), with group boundaries inside tiles and a group
-    whose series are all empty (not kept: it emits nothing)."""
+    (bucket, tile of KT_M members), with group boundaries inside tiles and a
+    group whose series are all empty (not kept: it emits nothing)."""
     import numpy as np
     from opentsdb_amd.batch import HostBatch
     b = datasets.random_batch(79, n_series=300, n_groups=3,
@@ -575,9 +575,9 @@ def test_percentiles_fill_several_large_groups(engine):
 def test_percentiles_fill_keys_fold_windows(engine, n_series, n_groups):
     """Fill-mode percentiles with every group large over wide grids (6 h of
     1 m / 10 s buckets: 360 / 2,160 of them) — the keys transpose's fill and
-    counts per (bucket, 64-member tile) with group boundaries inside tiles,
-    series that start late or end early (the fill before / after them), NaN
-    values, empty series (not kept): bit-exact with the oracle."""
+    counts per (bucket, tile of KT_M members) with group boundaries inside
+    tiles, series that start late or end early (the fill before / after
+    them), NaN values, empty series (not kept): bit-exact with the oracle."""
     b = datasets.random_batch(83 + n_series, n_series=n_series,
                               n_groups=n_groups, span_ms=6 * 3600 * 1000,
                               cadence_ms=20000, nan_frac=0.03,
