@@ -284,6 +284,42 @@ otsdb_status otsdb_agg_run_device(otsdb_ctx* ctx, const otsdb_query_spec* spec,
                                   const otsdb_batch* batch, otsdb_result* out,
                                   void* hip_stream);
 
+/* ---- several aggregators over one downsample pass ----------------------- */
+/* The sub-queries of one panel that differ only in the cross-series
+ * aggregator (min / avg / max / p99 of the same metric, tags, range and
+ * downsampling): agg_ids[i] / interps[i] take the place of spec->agg_id /
+ * spec->interp (OTSDB_INTERP_DEFAULT: the aggregator's own), everything else
+ * in `spec` is shared.  The point stream is downsampled ONCE into the
+ * per-series bucket rows; the scalar aggregators read the rows in one group
+ * pass, dev and the selections run their own group stage over the same rows
+ * (DESIGN.md §4).  Output i obeys exactly the contract of the single query
+ * with that aggregator; duplicates are allowed.  n_out outside
+ * [1, OTSDB_MULTI_MAX]: OTSDB_E_ILLEGAL_ARGUMENT; an unknown id:
+ * OTSDB_E_NO_SUCH_ELEMENT; when single queries of several outputs would fail
+ * the call fails with the status of the lowest-index one.  n_out == 1 is the
+ * single query.  Queries that cannot share the rows (raw group-by,
+ * per-series calendar anchors, OTSDB_SPEC_EXACT_ORDER dev past the row
+ * budget) run their outputs one after another: same results, nothing shared.
+ * plan_multi: max_out_points bounds EACH output, workspace_bytes the call.  */
+#define OTSDB_MULTI_MAX 32
+otsdb_status otsdb_agg_plan_multi(otsdb_ctx* ctx, const otsdb_query_spec* spec,
+                                  int32_t n_out, const int32_t* agg_ids,
+                                  const int32_t* interps,
+                                  const otsdb_batch* batch, otsdb_sizes* out);
+/* outs: n_out results (HOST array of structs; DEVICE pointers inside).      */
+otsdb_status otsdb_agg_run_multi_device(otsdb_ctx* ctx,
+                                        const otsdb_query_spec* spec,
+                                        int32_t n_out, const int32_t* agg_ids,
+                                        const int32_t* interps,
+                                        const otsdb_batch* batch,
+                                        otsdb_result* outs, void* hip_stream);
+/* Host pointers throughout; otsdb_agg_run's OTSDB_E_CAPACITY contract holds
+ * per result (the offsets of a result too small are still whole).           */
+otsdb_status otsdb_agg_run_multi(otsdb_ctx* ctx, const otsdb_query_spec* spec,
+                                 int32_t n_out, const int32_t* agg_ids,
+                                 const int32_t* interps,
+                                 const otsdb_batch* batch, otsdb_result* outs);
+
 /* ---- multi-GPU (series-sharded) ----------------------------------------- */
 /* Partial per-(group, bucket) reduction state, the unit exchanged between
  * ranks over RCCL.  32 bytes, see DESIGN.md §Multi-GPU.                     */
@@ -458,6 +494,18 @@ otsdb_status otsdb_agg_run_cells_device(otsdb_ctx* ctx,
                                         const otsdb_cells* cells,
                                         const otsdb_batch* batch,
                                         otsdb_result* out, void* hip_stream);
+/* Several aggregators over one decode + downsample of the columns
+ * (otsdb_agg_run_multi_device's contract; the routing between the fused
+ * decode and the columnar buffer is otsdb_agg_run_cells_device's).          */
+otsdb_status otsdb_agg_run_cells_multi_device(otsdb_ctx* ctx,
+                                              const otsdb_query_spec* spec,
+                                              int32_t n_out,
+                                              const int32_t* agg_ids,
+                                              const int32_t* interps,
+                                              const otsdb_cells* cells,
+                                              const otsdb_batch* batch,
+                                              otsdb_result* outs,
+                                              void* hip_stream);
 /* The same with HOST pointers (the JNI entry at the TsdbQuery seam: the
  * Spans' RowSeq bytes, SpanGroup members); copies in, runs, copies the
  * result out.  Synchronous.  row_series must be nondecreasing.            */
@@ -551,7 +599,10 @@ otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
  * out[1] with the general one, out[2] uniform folds that met a qualifier of
  * other flags and were re-run with the general kernel; out[3] passes over
  * the local key matrix and out[4] histogram passes of the last otsdb_sel_*
- * session.                                                                 */
+ * session.  Of the last otsdb_agg_*_multi* call: out[5] downsample
+ * (bucketize) passes over the point stream, out[6] group-stage passes over
+ * a row matrix, out[7] key transposes, out[8] transform passes (one per
+ * interpolation class).                                                    */
 otsdb_status otsdb_ctx_counters(otsdb_ctx* ctx, int64_t* out, int n);
 /* Test hook: the one-pass compaction's epoch (1 .. 2^24 - 1, forward only)
  * the context's next call increments, so tests can drive it to its wrap.  */

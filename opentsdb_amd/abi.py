@@ -150,7 +150,11 @@ EXPORTS = [
     "otsdb_encode_cells_device", "otsdb_agg_run_cells_device",
     "otsdb_compact_rows_device", "otsdb_span_assemble_device",
     "otsdb_agg_run_raw_device", "otsdb_agg_run_raw", "otsdb_agg_run_cells",
+    "otsdb_agg_plan_multi", "otsdb_agg_run_multi_device",
+    "otsdb_agg_run_multi", "otsdb_agg_run_cells_multi_device",
 ]
+
+MULTI_MAX = 32  # OTSDB_MULTI_MAX
 
 _lib = None
 
@@ -240,6 +244,18 @@ def load(path=None):
     lib.otsdb_agg_run_raw.restype = C.c_int
     lib.otsdb_agg_run_cells.argtypes = [vp, PS, PC, PB, PR]
     lib.otsdb_agg_run_cells.restype = C.c_int
+    # several aggregators over one downsample pass: (ctx, spec, n_out,
+    # agg_ids, interps, [cells,] batch, sizes | results[n_out] [, stream])
+    lib.otsdb_agg_plan_multi.argtypes = [vp, PS, i32, vp, vp, PB,
+                                         C.POINTER(Sizes)]
+    lib.otsdb_agg_plan_multi.restype = C.c_int
+    lib.otsdb_agg_run_multi_device.argtypes = [vp, PS, i32, vp, vp, PB, PR, vp]
+    lib.otsdb_agg_run_multi_device.restype = C.c_int
+    lib.otsdb_agg_run_multi.argtypes = [vp, PS, i32, vp, vp, PB, PR]
+    lib.otsdb_agg_run_multi.restype = C.c_int
+    lib.otsdb_agg_run_cells_multi_device.argtypes = [vp, PS, i32, vp, vp, PC,
+                                                     PB, PR, vp]
+    lib.otsdb_agg_run_cells_multi_device.restype = C.c_int
     lib.otsdb_prof_enable.argtypes = [vp, C.c_int]
     lib.otsdb_prof_enable.restype = C.c_int
     lib.otsdb_prof_read.argtypes = [vp, vp, vp, C.c_int, C.c_int]

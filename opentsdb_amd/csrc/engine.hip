@@ -30,6 +30,7 @@
 #include "raw.hip"
 #include "rows.hip"
 #include "calendar.hip"
+#include "multi.hip"
 #include "launch.h"
 
 using namespace otsdb;
@@ -279,6 +280,18 @@ struct otsdb_ctx {
   bool err_clean = false;
   bool clean_entry = false;
   bool small_ready = false;  // k_compact1 wrote {error word, total}
+  // multi-aggregator calls (otsdb_agg_run_multi*): one device error word per
+  // output, and per output the compaction's {error word, total, look-back
+  // mark, -} in mapped host memory (the call synchronises once, at its end)
+  int* d_merr = nullptr;
+  int64_t* h_mdone = nullptr;
+  int64_t* d_mdone = nullptr;
+  int multi_failed = -1;  // the output whose status the last multi call returned
+  int64_t multi_total[OTSDB_MULTI_MAX] = {0};  // points of each output
+  // otsdb_ctx_counters [5..8], of the last multi call: downsample passes over
+  // the point stream, group-stage passes over a row matrix, key transposes,
+  // transform passes
+  int64_t n_multi_ds = 0, n_multi_group = 0, n_multi_kt = 0, n_multi_tf = 0;
   // cross-rank selection session (otsdb_sel_*): lives in `ws` between calls
   struct {
     bool active = false;
@@ -467,6 +480,17 @@ otsdb_status make_cal_params(const otsdb_query_spec* s, Params* P,
   return OTSDB_OK;
 }
 
+// What of Params depends on the cross-series aggregator (a multi-aggregator
+// call sets it per output over one shared grid).
+void agg_params(Params* P, int agg_id, int interp) {
+  P->interp = interp >= 0 ? interp : kAggs[agg_id].interp;
+  P->pct = agg_id >= OTSDB_AGG_P999 ? pct_of(agg_id) : 0.0;
+  P->pct_est = agg_id < OTSDB_AGG_P999   ? 0
+               : agg_id < OTSDB_AGG_EP999R3 ? 0
+               : agg_id < OTSDB_AGG_EP999R7 ? 3
+                                            : 7;
+}
+
 // Grid of buckets every series row is laid out on.
 otsdb_status make_params(const otsdb_query_spec* s, Params* P,
                          otsdb_ctx* c = nullptr) {
@@ -480,13 +504,8 @@ otsdb_status make_params(const otsdb_query_spec* s, Params* P,
   P->drop_resets = s->drop_resets;
   P->counter_max = s->counter_max;
   P->reset_value = s->reset_value;
-  P->interp = s->interp >= 0 ? s->interp : kAggs[s->agg_id].interp;
+  agg_params(P, s->agg_id, s->interp);
   P->fill_value = (P->fill == OTSDB_FILL_ZERO) ? 0.0 : NAN;
-  P->pct = s->agg_id >= OTSDB_AGG_P999 ? pct_of(s->agg_id) : 0.0;
-  P->pct_est = s->agg_id < OTSDB_AGG_P999   ? 0
-               : s->agg_id < OTSDB_AGG_EP999R3 ? 0
-               : s->agg_id < OTSDB_AGG_EP999R7 ? 3
-                                               : 7;
   if (!(s->ds_interval_ms > 0 || s->run_all)) return OTSDB_OK;  // raw
   if (is_selection(s->ds_agg_id)) {
     P->ds_sel = s->ds_agg_id == OTSDB_AGG_MEDIAN ? 1 : 2;
@@ -790,13 +809,14 @@ template <class M>
 void launch_combine(otsdb_ctx* c, const Work& W, int64_t NB, int64_t n,
                     const int64_t* g, const int64_t* t0, const int64_t* t1,
                     double* out_val, uint8_t* out_emit, Packed* out_partial,
-                    bool two_level, int keep_empty = 0) {
+                    bool two_level, int keep_empty = 0, int* err = nullptr) {
   hipStream_t st = c->stream;
+  if (!err) err = c->d_err;
   if (!two_level) {
     hipLaunchKernelGGL(k_combine<M>, dim3(blocks_for(n * NB, 256)), dim3(256),
                        0, st, NB, n, g, t0, t1, (const Packed*)W.partial,
                        (const uint8_t*)W.tile_emit, out_val, out_emit,
-                       out_partial, c->d_err, (int64_t)0, keep_empty);
+                       out_partial, err, (int64_t)0, keep_empty);
     return;
   }
   hipLaunchKernelGGL(k_combine_l1<M>,
@@ -807,7 +827,7 @@ void launch_combine(otsdb_ctx* c, const Work& W, int64_t NB, int64_t n,
   hipLaunchKernelGGL(k_combine<M>, dim3(blocks_for(n * NB, 256)), dim3(256), 0,
                      st, NB, n, g, t0, t1, (const Packed*)W.comb,
                      (const uint8_t*)W.comb_emit, out_val, out_emit,
-                     out_partial, c->d_err, kCombineSlices, keep_empty);
+                     out_partial, err, kCombineSlices, keep_empty);
 }
 
 // The per-downsampler kernels live in one translation unit per downsampling
@@ -832,6 +852,202 @@ DsLaunch ds_args(otsdb_ctx* c, const Params& P, const BatchDev& B,
 bool fold_path(const otsdb_query_spec* spec, const Params& P, int mode) {
   return !P.ds_sel && !P.rate && !P.run_all && !is_selection(spec->agg_id) &&
          mode != 2;
+}
+
+// ---- the row path, part 1: "build the rows" ------------------------------
+// Per-series bucket rows W.R from the point stream (or the compacted
+// columns): prep + k_bucketize_k / the rate-fused ring / k_ds_select /
+// k_bucketize_cells.  Nothing here depends on the cross-series aggregator,
+// so a multi-aggregator call runs it once.
+otsdb_status build_rows(otsdb_ctx* c, const otsdb_query_spec* spec,
+                        const Params& P, const BatchDev& B, const Work& W,
+                        const CellsDev* cells, const int64_t* series_row,
+                        bool rate_fused) {
+  hipStream_t st = c->stream;
+  const int64_t S = B.S;
+  DsLaunch a = ds_args(c, P, B, W);
+  bool ok = true;
+  if (cells) {
+    // decode fused into the downsample (decode.hip)
+    ok = with_monoid(spec->ds_agg_id, [&](auto tag) {
+      using M = decltype(tag);
+      StageTimer tm(c, 0);
+      a.cells = *cells;
+      a.series_row = series_row;
+      launch_ds<M>(DS_CELLS, a);
+    });
+  } else if (P.ds_sel) {
+    // median / percentile downsampling: per-bucket selection
+    {
+      StageTimer tm(c, 3);
+      launch_ds<MSum<3>>(DS_PREP, a);
+    }
+    StageTimer tm(c, 0);
+    hipLaunchKernelGGL(k_ds_select, dim3((unsigned)S), dim3(64), 0, st, P, B,
+                       W.SM, W.R);
+  } else {
+    ok = with_monoid(spec->ds_agg_id, [&](auto tag) {
+      using M = decltype(tag);
+      {
+        StageTimer tm(c, 3);
+        launch_ds<M>(DS_PREP, a);
+      }
+      StageTimer tm(c, 0);
+      if (rate_fused) {
+        // RateSpan fused into the ring flush (1,024-bucket ring: a step
+        // hands its series back only across a gap of ~1,000 buckets); then
+        // the plain ring kernel for the series handed back
+        a.P.redo = W.redo;
+        launch_ds<M>(DS_RATE, a);
+        a.P.only_redo = 1;
+        launch_ds<M>(DS_RING, a);
+      } else {
+        launch_ds<M>(DS_RING, a);
+      }
+    });
+  }
+  if (!ok) return fail(OTSDB_E_UNSUPPORTED, "downsampler %d", spec->ds_agg_id);
+  return OTSDB_OK;
+}
+
+// ---- the row path, part 2: "aggregate the rows" --------------------------
+// k_transform in place: what each series contributes at every bucket (fill,
+// rate, interpolation P.interp).
+void transform_rows(otsdb_ctx* c, Params& P, const BatchDev& B, const Work& W,
+                    bool rate_fused) {
+  StageTimer tm(c, 1);
+  if (rate_fused) {  // only the series the fused kernel handed back
+    P.redo = W.redo;
+    P.only_redo = 1;
+  }
+  hipLaunchKernelGGL(k_transform<0>, dim3(blocks_for(B.S, 4)), dim3(256), 0,
+                     c->stream, P, B, W.SM, W.R, c->d_err);
+  P.only_redo = 0;
+}
+
+// what the group stage needs beside the rows, the tiles and the outputs
+struct AggStage {
+  const int64_t* d_members;
+  int64_t M;  // members of all groups
+  int mode;
+  bool fold, two_level;
+  Packed* gpart;
+  uint8_t* gemit;
+  const Packed* ginit;
+  const uint8_t* ginit_emit;
+};
+
+// percentiles over a FillingDownsampler grid with every group large: the
+// keys transpose applies the fill and counts, no k_transform / k_group
+// (cross-rank, mode 2: the same transpose; otsdb_sel_prepare_device
+// derives the counts from its per-tile counts)
+bool sel_fused_path(int agg_id, int mode, const Params& P, const Tiles& T,
+                    int64_t G) {
+  return is_selection(agg_id) && (mode == 0 || mode == 2) && P.sentinel &&
+         P.fill && !P.rate && !P.run_all && T.LG > 0 && T.LG == G;
+}
+
+otsdb_status sel_fused_keys(otsdb_ctx* c, const Params& P, const Work& W,
+                            const Tiles& T, int64_t NB, const AggStage& A) {
+  hipStream_t st = c->stream;
+  HIP_TRY(hipMemsetAsync(W.lg_kept, 0, (size_t)T.LG * 4, st));
+  SelFill F{W.SM.keep, W.SM.kf, W.SM.kl, P.fill_value, W.key_cnt,
+            T.lg_off, T.LG, W.lg_kept};
+  if (A.M > 0)
+    hipLaunchKernelGGL(k_keys_transpose<true>, kt_grid(A.M, NB),
+                       dim3(KT_THREADS), 0, st, NB, A.M, A.d_members, W.R,
+                       W.keys, W.key_mm, F);
+  return OTSDB_OK;
+}
+
+void sel_fused_select(otsdb_ctx* c, const Work& W, const Tiles& T, int64_t NB,
+                      const AggStage& A, int median, double pct,
+                      double* out_val, uint8_t* out_emit, int* err) {
+  const int64_t NSEG = T.LG * NB;
+  hipLaunchKernelGGL(k_seg_select, dim3((unsigned)NSEG), dim3(SS_THREADS), 0,
+                     c->stream, NB, A.M, T.LG, T.lg_g, T.lg_off, T.lg_k,
+                     (const uint64_t*)W.keys, (const SelState*)nullptr,
+                     (const uint8_t*)nullptr, out_val, err, median, pct,
+                     (const uint64_t*)W.key_mm, (const uint32_t*)W.key_cnt,
+                     (const uint32_t*)W.lg_kept, out_emit);
+}
+
+// n (non-NaN contributions) and the emit mask of every group, into
+// W.out_val / W.out_emit: the same for every selection over the same rows
+void sel_counts(otsdb_ctx* c, const Work& W, const Tiles& T, int64_t NB,
+                const AggStage& A, int* err) {
+  using MC = MSum<3>;
+  if (T.T > 0)
+    hipLaunchKernelGGL(k_group<MC>, dim3(blocks_for(T.T * NB, 256)), dim3(256),
+                       0, c->stream, NB, T.T, T.tg, T.tm0, T.tm1, T.single,
+                       A.d_members, W.R, W.partial, W.tile_emit, W.out_val,
+                       W.out_emit, err, 0, (const Packed*)nullptr,
+                       (const uint8_t*)nullptr);
+  if (T.MG > 0)
+    launch_combine<MC>(c, W, NB, T.MG, T.mg, T.mt0, T.mt1, W.out_val,
+                       W.out_emit, nullptr, A.two_level, 0, err);
+}
+
+// the rows' keys, member-major per bucket (read-only afterwards)
+void sel_keys(otsdb_ctx* c, const Work& W, int64_t NB, const AggStage& A) {
+  if (A.M > 0)
+    hipLaunchKernelGGL(k_keys_transpose<false>, kt_grid(A.M, NB),
+                       dim3(KT_THREADS), 0, c->stream, NB, A.M, A.d_members,
+                       W.R, W.keys, W.key_mm, SelFill{});
+}
+
+// one selection over counts (W.out_val / W.out_emit, overwritten with the
+// results) and keys; transpose: the keys are not built yet
+void sel_finish(otsdb_ctx* c, const Work& W, const Tiles& T, int64_t NB,
+                const AggStage& A, int median, double pct, bool transpose,
+                int* err) {
+  hipStream_t st = c->stream;
+  // groups of <= SEL_K series: sort in LDS
+  hipLaunchKernelGGL(k_group_select, dim3(blocks_for(T.T * NB, SEL_THREADS)),
+                     dim3(SEL_THREADS), 0, st, NB, T.T, T.tg, T.tm0, T.tm1,
+                     T.single, A.d_members, W.R, W.out_val, W.out_emit, err,
+                     median, pct);
+  // larger groups: radix select over transposed keys
+  if (T.LG > 0) {
+    const int64_t NSEG = T.LG * NB;
+    if (transpose) sel_keys(c, W, NB, A);
+    hipLaunchKernelGGL(k_sel_init, dim3(blocks_for(NSEG, 256)), dim3(256), 0,
+                       st, NB, T.LG, T.lg_g, (const double*)W.out_val,
+                       (const uint8_t*)W.out_emit, W.sel, median, pct);
+    // one workgroup per (group, bucket) segment: min/max, 11-bit digit
+    // passes until <= SS_CAP candidates, LDS gather + count select
+    hipLaunchKernelGGL(k_seg_select, dim3((unsigned)NSEG), dim3(SS_THREADS), 0,
+                       st, NB, A.M, T.LG, T.lg_g, T.lg_off, T.lg_k,
+                       (const uint64_t*)W.keys, (const SelState*)W.sel,
+                       (const uint8_t*)W.out_emit, W.out_val, err, median, pct,
+                       (const uint64_t*)W.key_mm, (const uint32_t*)nullptr,
+                       (const uint32_t*)nullptr, (uint8_t*)nullptr);
+  }
+}
+
+// a monoid aggregator: k_group over the rows (not after the ordered fold,
+// which left the tile partials itself), then the chunk merge
+otsdb_status group_rows(otsdb_ctx* c, int agg_id, const Work& W,
+                        const Tiles& T, int64_t NB, int64_t G,
+                        const AggStage& A, int* err) {
+  const bool ok = with_monoid(agg_id, [&](auto tag) {
+    using M = decltype(tag);
+    if (!A.fold && T.T > 0)
+      hipLaunchKernelGGL(k_group<M>, dim3(blocks_for(T.T * NB, 256)), dim3(256),
+                         0, c->stream, NB, T.T, T.tg, T.tm0, T.tm1, T.single,
+                         A.d_members, W.R, W.partial, W.tile_emit, W.out_val,
+                         W.out_emit, err, A.mode, A.ginit, A.ginit_emit);
+    if (A.mode == 0) {
+      if (T.MG > 0)
+        launch_combine<M>(c, W, NB, T.MG, T.mg, T.mt0, T.mt1, W.out_val,
+                          W.out_emit, nullptr, A.two_level, 0, err);
+    } else {
+      launch_combine<M>(c, W, NB, G, T.ag, T.at0, T.at1, W.out_val, A.gemit,
+                        A.gpart, A.two_level, A.ginit ? 1 : 0, err);
+    }
+  });
+  if (!ok) return fail(OTSDB_E_NO_SUCH_ELEMENT, "aggregator %d", agg_id);
+  return OTSDB_OK;
 }
 
 // Everything up to dense (group, bucket) results / partials.
@@ -1161,174 +1377,61 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
       }
     });
     if (!ok) return fail(OTSDB_E_UNSUPPORTED, "downsampler %d", spec->ds_agg_id);
-  } else if (cells && S > 0 && NB > 0) {
-    // decode fused into the downsample (decode.hip)
-    ok = with_monoid(spec->ds_agg_id, [&](auto tag) {
-      using M = decltype(tag);
-      StageTimer tm(c, 0);
-      a.cells = *cells;
-      a.series_row = series_row;
-      launch_ds<M>(DS_CELLS, a);
-    });
-    if (!ok) return fail(OTSDB_E_UNSUPPORTED, "downsampler %d", spec->ds_agg_id);
-  } else if (S > 0 && NB > 0 && P.ds_sel) {
-    // median / percentile downsampling: per-bucket selection
-    {
-      StageTimer tm(c, 3);
-      launch_ds<MSum<3>>(DS_PREP, a);
-    }
-    StageTimer tm(c, 0);
-    hipLaunchKernelGGL(k_ds_select, dim3((unsigned)S), dim3(64), 0, st, P, B,
-                       W.SM, W.R);
   } else if (S > 0 && NB > 0) {
-    ok = with_monoid(spec->ds_agg_id, [&](auto tag) {
-      using M = decltype(tag);
-      {
-        StageTimer tm(c, 3);
-        launch_ds<M>(DS_PREP, a);
-      }
-      StageTimer tm(c, 0);
-      if (rate_fused) {
-        // RateSpan fused into the ring flush (1,024-bucket ring: a step
-        // hands its series back only across a gap of ~1,000 buckets); then
-        // the plain ring kernel for the series handed back
-        a.P.redo = W.redo;
-        launch_ds<M>(DS_RATE, a);
-        a.P.only_redo = 1;
-        launch_ds<M>(DS_RING, a);
-      } else {
-        launch_ds<M>(DS_RING, a);
-      }
-    });
-    if (!ok) return fail(OTSDB_E_UNSUPPORTED, "downsampler %d", spec->ds_agg_id);
+    rc = build_rows(c, spec, P, B, W, cells, series_row, rate_fused);
+    if (rc) return rc;
   }
-  // percentiles over a FillingDownsampler grid with every group large: the
-  // keys transpose applies the fill and counts, no k_transform / k_group
-  // (cross-rank, mode 2: the same transpose; otsdb_sel_prepare_device
-  // derives the counts from its per-tile counts)
-  const bool sel_fused = is_selection(spec->agg_id) && (mode == 0 || mode == 2) &&
-                         P.sentinel && P.fill && !P.rate && !P.run_all &&
-                         T.LG > 0 && T.LG == G;
-  if (!fold && S > 0 && NB > 0 && !sel_fused) {
-    StageTimer tm(c, 1);
-    if (rate_fused) {  // only the series the fused kernel handed back
-      P.redo = W.redo;
-      P.only_redo = 1;
-    }
-    hipLaunchKernelGGL(k_transform<0>, dim3(blocks_for(S, 4)), dim3(256), 0,
-                       st, P, B, W.SM, W.R, c->d_err);
-    P.only_redo = 0;
-  }
+  const bool sel_fused = sel_fused_path(spec->agg_id, mode, P, T, G);
+  if (!fold && S > 0 && NB > 0 && !sel_fused)
+    transform_rows(c, P, B, W, rate_fused);
   if (G > 0 && NB > 0) {
     StageTimer tm(c, 2);
+    const AggStage A{d_members, goff.back(), mode, fold, two_level,
+                     gpart,     gemit,       ginit, ginit_emit};
     if (is_selection(spec->agg_id)) {
       if (mode == 1)
         return fail(OTSDB_E_UNSUPPORTED,
                     "percentiles across ranks: use the otsdb_sel_* protocol");
       const int median = spec->agg_id == OTSDB_AGG_MEDIAN ? 1 : 0;
       if (sel_fused) {
-        const int64_t M = goff.back();
-        const int64_t NSEG = T.LG * NB;
-        HIP_TRY(hipMemsetAsync(W.lg_kept, 0, (size_t)T.LG * 4, st));
-        SelFill F{W.SM.keep, W.SM.kf, W.SM.kl, P.fill_value, W.key_cnt,
-                  T.lg_off, T.LG, W.lg_kept};
-        if (M > 0)
-          hipLaunchKernelGGL(k_keys_transpose<true>, kt_grid(M, NB),
-                             dim3(KT_THREADS), 0, st, NB, M, d_members, W.R, W.keys,
-                             W.key_mm, F);
+        rc = sel_fused_keys(c, P, W, T, NB, A);
+        if (rc) return rc;
         W.sel_fused = true;
         if (mode == 2) {
           HIP_TRY(hipGetLastError());
           return OTSDB_OK;
         }
-        hipLaunchKernelGGL(k_seg_select, dim3((unsigned)NSEG), dim3(SS_THREADS),
-                           0, st, NB, M, T.LG, T.lg_g, T.lg_off, T.lg_k,
-                           (const uint64_t*)W.keys, (const SelState*)nullptr,
-                           (const uint8_t*)nullptr, W.out_val, c->d_err,
-                           median, P.pct, (const uint64_t*)W.key_mm,
-                           (const uint32_t*)W.key_cnt,
-                           (const uint32_t*)W.lg_kept, W.out_emit);
+        sel_fused_select(c, W, T, NB, A, median, P.pct, W.out_val, W.out_emit,
+                         c->d_err);
         HIP_TRY(hipGetLastError());
         return OTSDB_OK;
       }
-      // n (non-NaN contributions) and the emit mask of every group
-      using MC = MSum<3>;
-      if (T.T > 0)
-        hipLaunchKernelGGL(k_group<MC>, dim3(blocks_for(T.T * NB, 256)),
-                           dim3(256), 0, st, NB, T.T, T.tg, T.tm0, T.tm1,
-                           T.single, d_members, W.R, W.partial, W.tile_emit,
-                           W.out_val, W.out_emit, c->d_err, 0,
-                           (const Packed*)nullptr, (const uint8_t*)nullptr);
-      if (T.MG > 0)
-        launch_combine<MC>(c, W, NB, T.MG, T.mg, T.mt0, T.mt1, W.out_val,
-                           W.out_emit, nullptr, two_level);
+      sel_counts(c, W, T, NB, A, c->d_err);
       if (mode == 2) {
         // cross-rank protocol: local counts + keys only (otsdb_sel_*)
-        const int64_t M = goff.back();
-        if (M > 0)
-          hipLaunchKernelGGL(k_keys_transpose<false>,
-                             kt_grid(M, NB),
-                             dim3(KT_THREADS), 0, st, NB, M, d_members, W.R, W.keys,
-                             W.key_mm, SelFill{});
+        sel_keys(c, W, NB, A);
         HIP_TRY(hipGetLastError());
         return OTSDB_OK;
       }
-      // groups of <= SEL_K series: sort in LDS
-      hipLaunchKernelGGL(k_group_select,
-                         dim3(blocks_for(T.T * NB, SEL_THREADS)),
-                         dim3(SEL_THREADS), 0, st, NB, T.T, T.tg, T.tm0, T.tm1,
-                         T.single, d_members, W.R, W.out_val, W.out_emit,
-                         c->d_err, median, P.pct);
-      // larger groups: radix select over transposed keys
-      if (T.LG > 0) {
-        const int64_t M = goff.back();
-        const int64_t NSEG = T.LG * NB;
-        hipLaunchKernelGGL(k_keys_transpose<false>,
-                           kt_grid(M, NB),
-                           dim3(KT_THREADS), 0, st, NB, M, d_members, W.R, W.keys,
-                           W.key_mm, SelFill{});
-        hipLaunchKernelGGL(k_sel_init, dim3(blocks_for(NSEG, 256)), dim3(256),
-                           0, st, NB, T.LG, T.lg_g, (const double*)W.out_val,
-                           (const uint8_t*)W.out_emit, W.sel, median, P.pct);
-        // one workgroup per (group, bucket) segment: min/max, 11-bit digit
-        // passes until <= SS_CAP candidates, LDS gather + count select
-        hipLaunchKernelGGL(k_seg_select, dim3((unsigned)NSEG), dim3(SS_THREADS),
-                           0, st, NB, M, T.LG, T.lg_g, T.lg_off, T.lg_k,
-                           (const uint64_t*)W.keys, (const SelState*)W.sel,
-                           (const uint8_t*)W.out_emit, W.out_val, c->d_err,
-                           median, P.pct, (const uint64_t*)W.key_mm,
-                           (const uint32_t*)nullptr, (const uint32_t*)nullptr,
-                           (uint8_t*)nullptr);
-      }
+      sel_finish(c, W, T, NB, A, median, P.pct, /*transpose=*/true, c->d_err);
     } else {
-      ok = with_monoid(spec->agg_id, [&](auto tag) {
-        using M = decltype(tag);
-        if (!fold && T.T > 0)
-          hipLaunchKernelGGL(k_group<M>, dim3(blocks_for(T.T * NB, 256)),
-                             dim3(256), 0, st, NB, T.T, T.tg, T.tm0, T.tm1,
-                             T.single, d_members, W.R, W.partial, W.tile_emit,
-                             W.out_val, W.out_emit, c->d_err, mode, ginit,
-                             ginit_emit);
-        if (mode == 0) {
-          if (T.MG > 0)
-            launch_combine<M>(c, W, NB, T.MG, T.mg, T.mt0, T.mt1, W.out_val,
-                              W.out_emit, nullptr, two_level);
-        } else {
-          launch_combine<M>(c, W, NB, G, T.ag, T.at0, T.at1, W.out_val, gemit,
-                            gpart, two_level, ginit ? 1 : 0);
-        }
-      });
-      if (!ok) return fail(OTSDB_E_NO_SUCH_ELEMENT, "aggregator %d", spec->agg_id);
+      rc = group_rows(c, spec->agg_id, W, T, NB, G, A, c->d_err);
+      if (rc) return rc;
     }
   }
   HIP_TRY(hipGetLastError());
   return OTSDB_OK;
 }
 
+// err / small: the error word the compaction swaps out and where its
+// {error word, total} lands (default: the context's, read by finish)
 otsdb_status compact(otsdb_ctx* c, const Params& P, int64_t G,
                      const double* out_val, const uint8_t* out_emit,
-                     int64_t* counts, otsdb_result* out) {
+                     int64_t* counts, otsdb_result* out, int* err = nullptr,
+                     int64_t* small = nullptr) {
   hipStream_t st = c->stream;
+  if (!err) err = c->d_err;
+  if (!small) small = c->d_done;
   if (G == 0) {
     HIP_TRY(hipMemsetAsync(out->offsets, 0, sizeof(int64_t), st));
     return OTSDB_OK;
@@ -1360,7 +1463,6 @@ otsdb_status compact(otsdb_ctx* c, const Params& P, int64_t G,
   c->cmp_epoch = wrap ? 4u : c->cmp_epoch + 1;
   if (grow || wrap) HIP_TRY(hipMemsetAsync(p, 0, cap, st));  // no stale epochs
   unsigned long long* ticket = (unsigned long long*)((char*)c->d_err + 192);
-  int64_t* small = c->d_done;
   // few groups (C1's 100): one group (wavefront) per block, spread over more
   // CUs; many (C2's 10k): four per block (one wave per block ran C2's
   // compaction 0.20 -> 0.27 ms)
@@ -1370,7 +1472,7 @@ otsdb_status compact(otsdb_ctx* c, const Params& P, int64_t G,
                        dim3(64 * gpb), 0, st, P, G, out_val, out_emit,
                        (unsigned long long*)p, ticket, c->cmp_epoch,
                        out->offsets, out->capacity, out->ts, out->val,
-                       out->is_int, c->d_err, small);
+                       out->is_int, err, small);
   } else {
     int64_t* cnt = (int64_t*)p;
     hipLaunchKernelGGL(k_compact_count, dim3(blocks_for(G, gpb)),
@@ -1382,12 +1484,14 @@ otsdb_status compact(otsdb_ctx* c, const Params& P, int64_t G,
                        dim3(64 * gpb), 0, st, P, G, out_val, out_emit,
                        (const int64_t*)cnt, (const int64_t*)out->offsets,
                        out->capacity, out->ts, out->val, out->is_int,
-                       c->d_err, small);
+                       err, small);
   }
   HIP_TRY(hipGetLastError());
   c->small_ready = true;
   return OTSDB_OK;
 }
+
+otsdb_status result_status(int err, int64_t total, int64_t capacity);
 
 // reads the error word and the total point count; maps to a status
 otsdb_status finish(otsdb_ctx* c, int64_t G, otsdb_result* out) {
@@ -1416,8 +1520,15 @@ otsdb_status finish(otsdb_ctx* c, int64_t G, otsdb_result* out) {
                            hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
-  const int err = (int)(c->h_small[0] & 0xFFFFFFFF);
-  const int64_t total = c->h_small[1];
+  const otsdb_status rc = result_status((int)(c->h_small[0] & 0xFFFFFFFF),
+                                        c->h_small[1], out->capacity);
+  if (rc == OTSDB_E_CAPACITY)
+    c->result_short = true;  // the offsets are whole: the host entries return them
+  return rc;
+}
+
+// the status of one result: its device error word, then its capacity
+otsdb_status result_status(int err, int64_t total, int64_t capacity) {
   if (err & ERR_NONE_MULTI)
     return fail(OTSDB_E_ILLEGAL_DATA, "More than one value in aggregator raw");
   if (err & ERR_RATE_TS)
@@ -1441,11 +1552,9 @@ otsdb_status finish(otsdb_ctx* c, int64_t G, otsdb_result* out) {
                 "a point past the window lies outside the calendar table");
   if (err & ERR_INTERNAL)
     return fail(OTSDB_E_DEVICE, "internal: bucket outside the group row");
-  if (total > out->capacity) {
-    c->result_short = true;  // the offsets are whole: the host entries return them
+  if (total > capacity)
     return fail(OTSDB_E_CAPACITY, "result capacity %lld < %lld points",
-                (long long)out->capacity, (long long)total);
-  }
+                (long long)capacity, (long long)total);
   return OTSDB_OK;
 }
 
@@ -1831,6 +1940,488 @@ otsdb_status run_device_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   return finish(c, G, out);
 }
 
+// ------------------------------------------------ multi-aggregator queries
+// otsdb_agg_run_multi*: n outputs that differ in the cross-series aggregator
+// (and its interpolation) over one query.  DESIGN.md §4.
+struct MultiReq {
+  int32_t n;
+  const int32_t* aggs;
+  const int32_t* interps;  // null: every output its aggregator's own
+  otsdb_result* outs;
+};
+
+otsdb_query_spec multi_spec(const otsdb_query_spec* s, const MultiReq& q,
+                            int i) {
+  otsdb_query_spec r = *s;
+  r.agg_id = q.aggs[i];
+  r.interp = q.interps ? q.interps[i] : OTSDB_INTERP_DEFAULT;
+  return r;
+}
+
+otsdb_status check_multi(const otsdb_query_spec* spec, const MultiReq& q) {
+  if (q.n < 1 || q.n > OTSDB_MULTI_MAX)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "n_out %d outside [1, %d]", (int)q.n,
+                OTSDB_MULTI_MAX);
+  if (!q.aggs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null agg_ids");
+  for (int i = 0; i < q.n; ++i) {
+    const otsdb_query_spec si = multi_spec(spec, q, i);
+    const otsdb_status rc = check_spec(&si);
+    if (rc) return rc;
+  }
+  return OTSDB_OK;
+}
+
+enum { MK_SCALAR = 0, MK_ORDERED = 1, MK_SELECT = 2 };
+
+int multi_kind(int agg) {
+  if (is_selection(agg)) return MK_SELECT;
+  bool ordered = false;
+  with_monoid(agg, [&](auto tag) { ordered = decltype(tag)::kOrdered; });
+  return ordered ? MK_ORDERED : MK_SCALAR;
+}
+
+// The interpolation classes of the outputs: k_transform bakes P.interp into
+// the rows only for NONE fill without rate (its interpolation branch); the
+// fill branch and transform_rate never read it, so such queries have one
+// class.  cls[i]: class of output i; interp[k]: class k's interpolation.
+int multi_classes(const MultiReq& q, const Params& P, int* cls, int* interp) {
+  const bool baked = !(P.fill != 0 && !P.run_all) && !P.rate;
+  int n = 0;
+  for (int i = 0; i < q.n; ++i) {
+    const int m = !baked ? 0
+                  : (q.interps && q.interps[i] >= 0) ? q.interps[i]
+                                                     : kAggs[q.aggs[i]].interp;
+    int k = 0;
+    while (k < n && interp[k] != m) ++k;
+    if (k == n) interp[n++] = m;
+    cls[i] = k;
+  }
+  return n;
+}
+
+// Whether the outputs can share one row matrix.  Not: raw group-by,
+// per-series calendar anchors, nothing to aggregate, a grid the single path
+// would first trim to the data (past 4e9 cells), dev past the row budget
+// (with the pristine rows kept beside a class matrix: twice the rows).  Such
+// calls run their outputs one after another through the single-query path.
+bool multi_shares_rows(const otsdb_query_spec* spec, const MultiReq& q,
+                       const Params& P, int64_t S,
+                       const std::vector<int64_t>& goff) {
+  if (q.n < 2) return false;
+  if (!(spec->ds_interval_ms > 0 || spec->run_all) || anchored(spec))
+    return false;
+  const int64_t G = (int64_t)goff.size() - 1;
+  if (S <= 0 || G <= 0 || P.nb <= 0 || goff.back() <= 0) return false;
+  if (P.nb > (int64_t)INT32_MAX - 2) return false;
+  const double rows = (double)S * (double)P.nb;
+  if (rows > 4.0e9) return false;
+  int cls[OTSDB_MULTI_MAX], ci[OTSDB_MULTI_MAX];
+  const int n_cls = multi_classes(q, P, cls, ci);
+  bool dev = false;
+  for (int i = 0; i < q.n; ++i) dev |= multi_kind(q.aggs[i]) == MK_ORDERED;
+  if (dev) {
+    int64_t kmax = 0;
+    for (int64_t g = 0; g < G; ++g) kmax = std::max(kmax, goff[g + 1] - goff[g]);
+    if (kmax > kOrderedFoldChunk &&
+        rows * 9.0 * (n_cls > 1 ? 2.0 : 1.0) > kOrderedRowBudget)
+      return false;
+  }
+  return true;
+}
+
+struct MultiState {
+  const otsdb_query_spec* spec;
+  MultiReq q;
+  BatchDev B;
+  const int64_t* d_members;
+  std::vector<int64_t>* goff;
+  Params P;
+  Work W;   // W.R: the downsampler's rows; W.out_*: the selections' counts
+  Rows R2;  // one interpolation class's matrix (several classes only)
+  int64_t S, G, NB;
+  int cls[OTSDB_MULTI_MAX], cls_interp[OTSDB_MULTI_MAX], n_cls;
+  int kind[OTSDB_MULTI_MAX];
+  double* out_val[OTSDB_MULTI_MAX];
+  uint8_t* out_emit[OTSDB_MULTI_MAX];
+  Packed* partial[kMultiSlots];
+  bool rate_fused, sel_fused, two_level, two_level_dev, exact, empty_group;
+  // tiles of the scalar outputs and the selections' count pass: the ones the
+  // single query reduces over, so that each output has its bits — the
+  // ordered fold's (groups up to kFoldChunk whole, larger ones in tiles of
+  // kFoldChunkLarge, merged in order) where the single query folds, else
+  // the row path's kChunk.  (The selections only count over them: groups
+  // of up to SEL_K = kFoldChunk members are one tile either way.)
+  int64_t chunk, whole;
+};
+
+otsdb_status multi_buffers(otsdb_ctx* c) {
+  if (c->d_merr) return OTSDB_OK;
+  HIP_TRY(hipMalloc(&c->d_merr, OTSDB_MULTI_MAX * sizeof(int)));
+  HIP_TRY(hipHostMalloc(&c->h_mdone, OTSDB_MULTI_MAX * 4 * sizeof(int64_t),
+                        hipHostMallocMapped | hipHostMallocCoherent));
+  HIP_TRY(hipHostGetDevicePointer((void**)&c->d_mdone, c->h_mdone, 0));
+  for (int i = 0; i < OTSDB_MULTI_MAX * 4; ++i) c->h_mdone[i] = 0;
+  return OTSDB_OK;
+}
+
+// "Build the rows" once for every output: the tiles, the workspace of the
+// whole call and the downsample pass (fold off: the rows are what is
+// shared).  cells: as run_pipeline's.
+otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
+                         const MultiReq& q, const BatchDev& B,
+                         const int64_t* d_members, std::vector<int64_t>& goff,
+                         const Params& P0, const CellsDev* cells,
+                         const int64_t* series_row, MultiState& M) {
+  hipStream_t st = c->stream;
+  otsdb_status rc = multi_buffers(c);
+  if (rc) return rc;
+  M.spec = spec;
+  M.q = q;
+  M.B = B;
+  M.d_members = d_members;
+  M.goff = &goff;
+  M.P = P0;
+  Params& P = M.P;
+  const int64_t S = M.S = B.S;
+  const int64_t G = M.G = (int64_t)goff.size() - 1;
+  const int64_t NB = M.NB = P.nb;
+  P.fold_wb = 0;
+  P.fold_ctx = 0;
+  P.sentinel = !cells && !P.ds_sel;
+  M.rate_fused = P.sentinel && P.rate && !P.fill && !P.run_all;
+  M.exact = (spec->flags & OTSDB_SPEC_EXACT_ORDER) != 0;
+  M.n_cls = multi_classes(q, P, M.cls, M.cls_interp);
+  uint32_t mask = 0;
+  bool any_sel = false, all_sel = true;
+  for (int i = 0; i < q.n; ++i) {
+    M.kind[i] = multi_kind(q.aggs[i]);
+    any_sel |= M.kind[i] == MK_SELECT;
+    all_sel &= M.kind[i] == MK_SELECT;
+    if (M.kind[i] == MK_SCALAR)
+      with_monoid(q.aggs[i], [&](auto tag) {
+        constexpr int k = MultiSlot<decltype(tag)>::value;
+        if (k >= 0) mask |= 1u << (k & 31);
+      });
+  }
+  const bool folds = !P.ds_sel && !P.rate && !P.run_all &&
+                     !(cells && !P.narrow) && kFoldChunk >= (int64_t)SEL_K;
+  M.chunk = folds ? kFoldChunkLarge : kChunk;
+  M.whole = folds ? kFoldChunk : 0;
+  rc = build_tiles(c, goff, false, M.chunk, M.whole);
+  if (rc) return rc;
+  const Tiles T = tiles_of(c, G);
+  M.sel_fused = all_sel && sel_fused_path(q.aggs[0], 0, P, T, G);
+  const bool sel_large = any_sel && T.LG > 0;
+  M.two_level = T.max_chunks > kCombineL1 &&
+                (double)T.MG * kCombineSlices * NB * 33.0 < 2.0e9;
+  // dev's own tiles (one chain per group up to kOrderedChunk members): how
+  // many groups its merge covers, and its longest
+  int64_t mg_dev = 0, max_dev = 0;
+  const int64_t whole = M.exact ? INT64_MAX : kOrderedChunk;
+  M.empty_group = false;
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t k = goff[g + 1] - goff[g];
+    M.empty_group |= k == 0;
+    if (k > whole) {
+      ++mg_dev;
+      max_dev = std::max(max_dev, (k + kChunk - 1) / kChunk);
+    }
+  }
+  M.two_level_dev = max_dev > kCombineL1 &&
+                    (double)mg_dev * kCombineSlices * NB * 33.0 < 2.0e9;
+  const int64_t n_comb = std::max(M.two_level ? T.MG : 0,
+                                  M.two_level_dev ? mg_dev : 0);
+  const size_t rows = (size_t)S * NB;
+  Work& W = M.W;
+  auto carve = [&](char* base) {
+    Carve cv{base};
+    W.SM.lo = cv.take<int64_t>(S);
+    W.SM.hi = cv.take<int64_t>(S);
+    W.SM.of_ts = cv.take<int64_t>(S);
+    W.SM.of_val = cv.take<double>(S);
+    W.SM.of_rate = cv.take<double>(S);
+    W.SM.kf = cv.take<int32_t>(S);
+    W.SM.kl = cv.take<int32_t>(S);
+    W.SM.keep = cv.take<uint8_t>(S);
+    W.SM.of_has = cv.take<uint8_t>(S);
+    W.redo = cv.take<uint8_t>(S);
+    W.R.val = cv.take<double>(rows);
+    W.R.state = cv.take<uint8_t>(rows);
+    M.R2 = Rows{nullptr, nullptr};
+    if (M.n_cls > 1) {
+      M.R2.val = cv.take<double>(rows);
+      M.R2.state = cv.take<uint8_t>(rows);
+    }
+    // one partial slot per requested monoid (slot 0 always: the selections'
+    // count pass and dev borrow it between launches)
+    for (int k = 0; k < kMultiSlots; ++k)
+      M.partial[k] = (k == 0 || (mask >> k & 1))
+                         ? cv.take<Packed>((size_t)T.T * NB)
+                         : nullptr;
+    W.partial = M.partial[0];
+    W.tile_emit = cv.take<uint8_t>((size_t)T.T * NB);
+    W.out_val = cv.take<double>((size_t)G * NB);
+    W.out_emit = cv.take<uint8_t>((size_t)G * NB);
+    for (int i = 0; i < q.n; ++i) {
+      M.out_val[i] = cv.take<double>((size_t)G * NB);
+      M.out_emit[i] = cv.take<uint8_t>((size_t)G * NB);
+    }
+    W.counts = nullptr;
+    if (n_comb > 0) {
+      W.comb = cv.take<Packed>((size_t)n_comb * kCombineSlices * NB);
+      W.comb_emit = cv.take<uint8_t>((size_t)n_comb * kCombineSlices * NB);
+    }
+    if (sel_large) {
+      W.keys = cv.take<uint64_t>((size_t)goff.back() * NB);
+      W.key_mm = cv.take<uint64_t>((size_t)((goff.back() + KT_M - 1) / KT_M) * NB * 2);
+      W.key_cnt = cv.take<uint32_t>((size_t)((goff.back() + KT_M - 1) / KT_M) * NB);
+      W.lg_kept = cv.take<uint32_t>((size_t)T.LG + 1);
+      W.sel = cv.take<SelState>((size_t)T.LG * NB);
+    }
+    return cv.off + 256;
+  };
+  rc = ensure(&c->ws, &c->ws_cap, carve(nullptr));
+  if (rc) return rc;
+  carve((char*)c->ws);
+
+  // every output its own error word; the shared stages report into the
+  // context's (folded into every output's status at the end)
+  HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(int), st));
+  HIP_TRY(hipMemsetAsync(c->d_merr, 0, OTSDB_MULTI_MAX * sizeof(int), st));
+  c->clean_entry = false;
+  if (M.empty_group) {
+    HIP_TRY(hipMemsetAsync(W.out_emit, 0, (size_t)G * NB, st));
+    for (int i = 0; i < q.n; ++i)
+      HIP_TRY(hipMemsetAsync(M.out_emit[i], 0, (size_t)G * NB, st));
+  }
+  if (!P.sentinel) HIP_TRY(hipMemsetAsync(W.R.state, 0, rows, st));
+  c->n_multi_ds = c->n_multi_group = c->n_multi_kt = c->n_multi_tf = 0;
+  rc = build_rows(c, spec, P, B, W, cells, series_row, M.rate_fused);
+  if (rc) return rc;
+  ++c->n_multi_ds;
+  HIP_TRY(hipGetLastError());
+  return OTSDB_OK;
+}
+
+// "Aggregate the rows" per interpolation class and output, compact every
+// output into its result, synchronise once and report the status of the
+// lowest-index failing output.
+otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M) {
+  hipStream_t st = c->stream;
+  const MultiReq& q = M.q;
+  const int64_t G = M.G, NB = M.NB, S = M.S;
+  Params& P = M.P;
+  otsdb_status rc;
+  auto stage = [&](const Tiles& T, bool two_level) {
+    return AggStage{M.d_members, M.goff->back(), 0,       false, two_level,
+                    nullptr,     nullptr,        nullptr, nullptr};
+  };
+  auto sel_of = [&](int i, int* median, double* pct) {
+    *median = q.aggs[i] == OTSDB_AGG_MEDIAN ? 1 : 0;
+    *pct = q.aggs[i] >= OTSDB_AGG_P999 ? pct_of(q.aggs[i]) : 0.0;
+  };
+  if (M.sel_fused) {
+    // every output a selection over a filling grid of large groups: the one
+    // transpose applies the fill and counts, then one select per output
+    StageTimer tm(c, 2);
+    const Tiles T = tiles_of(c, G);
+    const AggStage A = stage(T, M.two_level);
+    rc = sel_fused_keys(c, P, M.W, T, NB, A);
+    if (rc) return rc;
+    ++c->n_multi_kt;
+    for (int i = 0; i < q.n; ++i) {
+      int median;
+      double pct;
+      sel_of(i, &median, &pct);
+      sel_fused_select(c, M.W, T, NB, A, median, pct, M.out_val[i],
+                       M.out_emit[i], c->d_merr + i);
+      ++c->n_multi_group;
+    }
+  }
+  for (int k = 0; k < M.n_cls && !M.sel_fused; ++k) {
+    Work Wc = M.W;  // this class's matrix
+    if (M.n_cls == 1) {
+      P.interp = M.cls_interp[0];
+      transform_rows(c, P, M.B, M.W, M.rate_fused);
+    } else {
+      StageTimer tm(c, 1);
+      Params Pc = P;
+      Pc.interp = M.cls_interp[k];
+      if (!P.sentinel) HIP_TRY(hipMemsetAsync(M.R2.state, 0, (size_t)S * NB, st));
+      hipLaunchKernelGGL(k_transform_interp, dim3(blocks_for(S, 4)), dim3(256),
+                         0, st, Pc, M.B, M.W.SM, M.W.R, M.R2);
+      Wc.R = M.R2;
+    }
+    ++c->n_multi_tf;
+    StageTimer tm(c, 2);
+    rc = build_tiles(c, *M.goff, false, M.chunk, M.whole);  // (cached unless dev ran)
+    if (rc) return rc;
+    const Tiles T = tiles_of(c, G);
+    const AggStage A = stage(T, M.two_level);
+    // ---- the scalar, unordered outputs: one pass for all of them
+    MultiArgs MA{};
+    int who[OTSDB_MULTI_MAX];
+    for (int i = 0; i < q.n; ++i) {
+      if (M.cls[i] != k || M.kind[i] != MK_SCALAR) continue;
+      const int j = MA.n_out++;
+      who[j] = i;
+      with_monoid(q.aggs[i], [&](auto tag) {
+        MA.slot[j] = MultiSlot<decltype(tag)>::value;
+      });
+      MA.mask |= 1u << (MA.slot[j] & 31);
+      MA.out[j] = MultiOut{M.out_val[i], M.out_emit[i], c->d_merr + i};
+    }
+    for (int s = 0; s < kMultiSlots; ++s) MA.partial[s] = M.partial[s];
+    if (MA.n_out > 0 && T.T > 0) {
+      hipLaunchKernelGGL(k_group_multi, dim3(blocks_for(T.T * NB, 256)),
+                         dim3(256), 0, st, NB, T.T, T.tg, T.tm0, T.tm1,
+                         T.single, M.d_members, Wc.R, M.W.tile_emit, MA);
+      ++c->n_multi_group;
+      if (T.MG > 0)
+        for (int j = 0; j < MA.n_out; ++j) {
+          const int i = who[j];
+          Work Ws = Wc;
+          Ws.partial = M.partial[MA.slot[j]];
+          with_monoid(q.aggs[i], [&](auto tag) {
+            launch_combine<decltype(tag)>(c, Ws, NB, T.MG, T.mg, T.mt0, T.mt1,
+                                          M.out_val[i], M.out_emit[i], nullptr,
+                                          M.two_level, 0, c->d_merr + i);
+          });
+        }
+    }
+    // ---- the selections: one count pass and one key transpose, then a
+    // select per output over the shared, read-only keys
+    bool counted = false;
+    for (int i = 0; i < q.n; ++i) {
+      if (M.cls[i] != k || M.kind[i] != MK_SELECT) continue;
+      if (!counted) {
+        sel_counts(c, Wc, T, NB, A, c->d_err);
+        ++c->n_multi_group;
+        if (T.LG > 0) {
+          sel_keys(c, Wc, NB, A);
+          ++c->n_multi_kt;
+        }
+        counted = true;
+      }
+      HIP_TRY(hipMemcpyAsync(M.out_val[i], Wc.out_val, (size_t)G * NB * 8,
+                             hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(M.out_emit[i], Wc.out_emit, (size_t)G * NB,
+                             hipMemcpyDeviceToDevice, st));
+      Work Wo = Wc;
+      Wo.out_val = M.out_val[i];
+      Wo.out_emit = M.out_emit[i];
+      int median;
+      double pct;
+      sel_of(i, &median, &pct);
+      sel_finish(c, Wo, T, NB, A, median, pct, /*transpose=*/false,
+                 c->d_merr + i);
+      ++c->n_multi_group;
+    }
+    // ---- the ordered outputs (dev): their own group pass over the tiles
+    // the single query's row path builds (one chain per group up to
+    // kOrderedChunk members, Chan's merge beyond, EXACT_ORDER honoured)
+    bool dev_tiles = false;
+    for (int i = 0; i < q.n; ++i) {
+      if (M.cls[i] != k || M.kind[i] != MK_ORDERED) continue;
+      if (!dev_tiles) {
+        rc = build_tiles(c, *M.goff, false, kChunk,
+                         M.exact ? INT64_MAX : kOrderedChunk);
+        if (rc) return rc;
+        dev_tiles = true;
+      }
+      const Tiles Td = tiles_of(c, G);
+      const AggStage Ad = stage(Td, M.two_level_dev);
+      Work Wd = Wc;
+      Wd.out_val = M.out_val[i];
+      Wd.out_emit = M.out_emit[i];
+      rc = group_rows(c, q.aggs[i], Wd, Td, NB, G, Ad, c->d_merr + i);
+      if (rc) return rc;
+      ++c->n_multi_group;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  // ---- every output through the existing compaction into its own result
+  for (int i = 0; i < q.n; ++i) {
+    Params Pi = P;
+    agg_params(&Pi, q.aggs[i], q.interps ? q.interps[i] : OTSDB_INTERP_DEFAULT);
+    rc = compact(c, Pi, G, M.out_val[i], M.out_emit[i], nullptr, &q.outs[i],
+                 c->d_merr + i, c->d_mdone + 4 * i);
+    if (rc) return rc;
+  }
+  // (the next call of any kind clears the context's word itself: err_clean
+  // stays false, as after a single query that did not end in k_compact1)
+  c->small_ready = false;
+  c->h_small[0] = 0;
+  HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
+                         hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int shared = (int)(c->h_small[0] & 0xFFFFFFFF);
+  for (int i = 0; i < q.n; ++i) {
+    int64_t* d = c->h_mdone + 4 * i;
+    int e = shared | (int)(__atomic_load_n(&d[0], __ATOMIC_ACQUIRE) & 0xFFFFFFFF);
+    c->multi_total[i] = __atomic_load_n(&d[1], __ATOMIC_ACQUIRE);
+    if (__atomic_load_n(&d[2], __ATOMIC_ACQUIRE)) {
+      d[2] = 0;
+      e |= ERR_INTERNAL;
+    }
+    rc = result_status(e, c->multi_total[i], q.outs[i].capacity);
+    if (rc) {
+      c->multi_failed = i;
+      if (rc == OTSDB_E_CAPACITY) c->result_short = true;
+      return rc;
+    }
+  }
+  return OTSDB_OK;
+}
+
+// The outputs one after another through the single-query path (what cannot
+// share the rows): the same results, nothing shared.
+otsdb_status multi_sequential(otsdb_ctx* c, const otsdb_query_spec* spec,
+                              const MultiReq& q, const otsdb_batch* b,
+                              std::vector<int64_t>& goff) {
+  c->n_multi_ds = c->n_multi_group = c->n_multi_kt = c->n_multi_tf = 0;
+  for (int i = 0; i < q.n; ++i) {
+    const otsdb_query_spec si = multi_spec(spec, q, i);
+    // the "error word known zero" mark is the last single query's alone
+    c->err_clean = false;
+    const otsdb_status rc = run_device_impl(c, &si, b, &q.outs[i], goff);
+    if (rc) {
+      c->multi_failed = i;
+      return rc;
+    }
+    c->multi_total[i] = c->h_small[1];
+    ++c->n_multi_ds;
+    ++c->n_multi_group;
+  }
+  return OTSDB_OK;
+}
+
+otsdb_status run_multi_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
+                            const MultiReq& q, const otsdb_batch* b,
+                            std::vector<int64_t>& goff) {
+  c->multi_failed = -1;
+  if (q.n == 1 || !(spec->ds_interval_ms > 0 || spec->run_all) ||
+      anchored(spec))
+    return multi_sequential(c, spec, q, b, goff);
+  const otsdb_query_spec s0 = multi_spec(spec, q, 0);
+  Params P;
+  otsdb_status rc = make_params(&s0, &P, c);
+  if (rc) {
+    c->multi_failed = 0;
+    return rc;
+  }
+  // (a misaligned batch: the single path reports it)
+  if (((((uintptr_t)b->ts_ms) | ((uintptr_t)b->val)) & 15) ||
+      !multi_shares_rows(spec, q, P, b->n_series, goff))
+    return multi_sequential(c, spec, q, b, goff);
+  BatchDev B{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
+             b->series_float};
+  MultiState M;
+  rc = multi_build(c, &s0, q, B, b->group_members, goff, P, nullptr, nullptr, M);
+  if (rc) return rc;
+  return multi_aggregate(c, M);
+}
+
 // otsdb_decode_cells_device without the lock (also the fallback of the
 // fused cells query)
 // counted: an earlier call on the same cells (ts_ms null) left the row
@@ -1976,9 +2567,14 @@ otsdb_status requal_impl(otsdb_ctx* c, const CellsDev& C, CellsDev* out,
 
 // Query straight from compacted columns: the fused decode + downsample when
 // the query and the columns allow it, else decode -> columnar -> pipeline.
+// mq: several aggregators (otsdb_agg_run_cells_multi_device; `spec` carries
+// output 0's, `out` is unused): the same routing, with the shared-rows
+// pipeline in place of run_pipeline where the outputs can share them, and
+// run_multi_impl over the decoded columns otherwise.
 otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
                             const otsdb_cells* cells, const otsdb_batch* b,
-                            otsdb_result* out, std::vector<int64_t>& goff) {
+                            otsdb_result* out, std::vector<int64_t>& goff,
+                            const MultiReq* mq = nullptr) {
   otsdb_status rc = check_spec(spec);
   if (rc) return rc;
   hipStream_t st = c->stream;
@@ -1994,7 +2590,8 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   }
   CellsDev C{R, cells->row_series, cells->row_base_s, cells->qual_off,
              cells->qual, cells->val_off, cells->val};
-  if (fused && !P.ds_sel && !P.run_all) {
+  if (fused && !P.ds_sel && !P.run_all &&
+      (!mq || multi_shares_rows(spec, *mq, P, S, goff))) {
     rc = ensure(&c->cells_ws, &c->cells_ws_cap, (size_t)(S + 1) * 8);
     if (rc) return rc;
     int64_t* series_row = (int64_t*)c->cells_ws;
@@ -2013,8 +2610,13 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
     bool requaled = false;
     for (int attempt = 0; attempt < 4; ++attempt) {
       Work W;
-      rc = run_pipeline(c, spec, B, b->group_members, goff, P, W, 0, nullptr,
-                        nullptr, &CQ, series_row);
+      MultiState MS;
+      if (mq)
+        rc = multi_build(c, spec, *mq, B, b->group_members, goff, P, &CQ,
+                         series_row, MS);
+      else
+        rc = run_pipeline(c, spec, B, b->group_members, goff, P, W, 0, nullptr,
+                          nullptr, &CQ, series_row);
       if (rc) return rc;
       HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
                              hipMemcpyDeviceToHost, st));
@@ -2032,6 +2634,7 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
         return fail(OTSDB_E_ILLEGAL_DATA,
                     "Corrupted value: couldn't break down into individual values");
       if (!(e & ERR_CELLS_GENERIC)) {
+        if (mq) return multi_aggregate(c, MS);
         const int64_t G = (int64_t)goff.size() - 1;
         rc = compact(c, P, G, W.out_val, W.out_emit, W.counts, out);
         if (rc) return rc;
@@ -2080,6 +2683,7 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   cb.val = vv;
   cb.is_float = isf;
   cb.series_float = nullptr;
+  if (mq) return run_multi_impl(c, spec, *mq, &cb, goff);
   return run_device_impl(c, spec, &cb, out, goff);
 }
 
@@ -2629,6 +3233,8 @@ void otsdb_ctx_destroy(otsdb_ctx* c) {
   if (c->sel.segmem) hipFree(c->sel.segmem);
   if (c->cmp_flags) hipFree(c->cmp_flags);
   if (c->d_err) hipFree(c->d_err);
+  if (c->d_merr) hipFree(c->d_merr);
+  if (c->h_mdone) hipHostFree(c->h_mdone);
   for (auto e : c->ev_pool) hipEventDestroy(e);
   if (c->h_small) hipHostFree(c->h_small);
   if (c->h_done) hipHostFree(c->h_done);
@@ -2714,9 +3320,11 @@ otsdb_status otsdb_agg_run_cells_device(otsdb_ctx* c,
   return rc;
 }
 
-otsdb_status otsdb_agg_run(otsdb_ctx* c, const otsdb_query_spec* spec,
-                           const otsdb_batch* b, otsdb_result* out) {
-  if (!c || !spec || !b || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+// The host-pointer entries: the batch staged in HBM once, n results (mq: the
+// multi-aggregator request whose results `outs` are, else one single query).
+static otsdb_status run_host(otsdb_ctx* c, const otsdb_query_spec* spec,
+                             const otsdb_batch* b, int n, otsdb_result* outs,
+                             const MultiReq* mq) {
   CtxLock lk(c);
   HIP_TRY(hipSetDevice(c->device));
   std::vector<int64_t> goff;
@@ -2730,11 +3338,10 @@ otsdb_status otsdb_agg_run(otsdb_ctx* c, const otsdb_query_spec* spec,
   for (int64_t m = 0; m < M; ++m)
     if (b->group_members[m] < 0 || b->group_members[m] >= S)
       return fail(OTSDB_E_ILLEGAL_ARGUMENT, "group member out of range");
-  const int64_t cap = out->capacity;
   // staging layout in HBM
   auto carve = [&](char* base) {
     Carve cv{base};
-    void* p[11];
+    std::vector<void*> p(7 + 4 * (size_t)n);
     p[0] = cv.take<int64_t>(S + 1);
     p[1] = cv.take<int64_t>(N + 1);
     p[2] = cv.take<int64_t>(N + 1);
@@ -2742,11 +3349,14 @@ otsdb_status otsdb_agg_run(otsdb_ctx* c, const otsdb_query_spec* spec,
     p[4] = b->series_float ? cv.take<uint8_t>(S + 1) : nullptr;
     p[5] = cv.take<int64_t>(G + 1);
     p[6] = cv.take<int64_t>(M + 1);
-    p[7] = cv.take<int64_t>(G + 1);
-    p[8] = cv.take<int64_t>(cap + 1);
-    p[9] = cv.take<int64_t>(cap + 1);
-    p[10] = cv.take<uint8_t>(cap + 1);
-    return std::make_pair(cv.off + 256, std::vector<void*>(p, p + 11));
+    for (int i = 0; i < n; ++i) {
+      const int64_t cap = outs[i].capacity;
+      p[7 + 4 * i] = cv.take<int64_t>(G + 1);
+      p[8 + 4 * i] = cv.take<int64_t>(cap + 1);
+      p[9 + 4 * i] = cv.take<int64_t>(cap + 1);
+      p[10 + 4 * i] = cv.take<uint8_t>(cap + 1);
+    }
+    return std::make_pair(cv.off + 256, p);
   };
   const size_t need = carve(nullptr).first;
   rc = ensure(&c->stage, &c->stage_cap, need);
@@ -2772,27 +3382,127 @@ otsdb_status otsdb_agg_run(otsdb_ctx* c, const otsdb_query_spec* spec,
   db.series_float = (const uint8_t*)pp[4];
   db.group_offsets = (const int64_t*)pp[5];
   db.group_members = (const int64_t*)pp[6];
-  otsdb_result dr;
-  dr.capacity = cap;
-  dr.offsets = (int64_t*)pp[7];
-  dr.ts = (int64_t*)pp[8];
-  dr.val = (int64_t*)pp[9];
-  dr.is_int = (uint8_t*)pp[10];
+  std::vector<otsdb_result> dr((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    dr[i].capacity = outs[i].capacity;
+    dr[i].offsets = (int64_t*)pp[7 + 4 * i];
+    dr[i].ts = (int64_t*)pp[8 + 4 * i];
+    dr[i].val = (int64_t*)pp[9 + 4 * i];
+    dr[i].is_int = (uint8_t*)pp[10 + 4 * i];
+  }
   c->result_short = false;
-  rc = run_device_impl(c, spec, &db, &dr, goff);
-  if (rc == OTSDB_E_CAPACITY && c->result_short)
-    return copy_offsets_back(c, out, dr.offsets, G, rc);
+  if (mq) {
+    MultiReq dq = *mq;
+    dq.outs = dr.data();
+    rc = run_multi_impl(c, spec, dq, &db, goff);
+  } else {
+    rc = run_device_impl(c, spec, &db, &dr[0], goff);
+  }
+  if (rc == OTSDB_E_CAPACITY && c->result_short) {
+    // the offsets of the result too small (and of those before it) are whole
+    const int last = mq ? c->multi_failed : 0;
+    for (int i = 0; i < last; ++i)
+      copy_offsets_back(c, &outs[i], dr[i].offsets, G, rc);
+    return copy_offsets_back(c, &outs[last], dr[last].offsets, G, rc);
+  }
   if (rc) return rc;
-  const int64_t total = c->h_small[1];
-  HIP_TRY(hipMemcpyAsync(out->offsets, dr.offsets, 8 * (G + 1),
-                         hipMemcpyDeviceToHost, st));
-  if (total > 0) {
-    HIP_TRY(hipMemcpyAsync(out->ts, dr.ts, 8 * total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->val, dr.val, 8 * total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->is_int, dr.is_int, total, hipMemcpyDeviceToHost, st));
+  for (int i = 0; i < n; ++i) {
+    const int64_t total = mq ? c->multi_total[i] : c->h_small[1];
+    otsdb_result* out = &outs[i];
+    HIP_TRY(hipMemcpyAsync(out->offsets, dr[i].offsets, 8 * (G + 1),
+                           hipMemcpyDeviceToHost, st));
+    if (total > 0) {
+      HIP_TRY(hipMemcpyAsync(out->ts, dr[i].ts, 8 * total, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(out->val, dr[i].val, 8 * total, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(out->is_int, dr[i].is_int, total, hipMemcpyDeviceToHost, st));
+    }
   }
   HIP_TRY(hipStreamSynchronize(st));
   return OTSDB_OK;
+}
+
+otsdb_status otsdb_agg_run(otsdb_ctx* c, const otsdb_query_spec* spec,
+                           const otsdb_batch* b, otsdb_result* out) {
+  if (!c || !spec || !b || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  return run_host(c, spec, b, 1, out, nullptr);
+}
+
+otsdb_status otsdb_agg_plan_multi(otsdb_ctx* c, const otsdb_query_spec* spec,
+                                  int32_t n_out, const int32_t* agg_ids,
+                                  const int32_t* interps, const otsdb_batch* b,
+                                  otsdb_sizes* out) {
+  if (!spec || !b || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  const MultiReq q{n_out, agg_ids, interps, nullptr};
+  otsdb_status rc = check_multi(spec, q);
+  if (rc) return rc;
+  const otsdb_query_spec s0 = multi_spec(spec, q, 0);
+  rc = otsdb_agg_plan(c, &s0, b, out);
+  if (rc) return rc;
+  // the bound of the point count holds for each output; the workspace: the
+  // downsampler's rows and one class matrix, every output's dense results
+  // and one tile partial per distinct reduction state
+  if (s0.ds_interval_ms > 0 || s0.run_all)
+    out->workspace_bytes =
+        b->n_series * (out->n_buckets * 18 + 48) +
+        (int64_t)(n_out + 1) * b->n_groups * (out->n_buckets * 9 + 8) +
+        (int64_t)kMultiSlots * (b->n_series / kChunk + b->n_groups) *
+            out->n_buckets * 33;
+  return OTSDB_OK;
+}
+
+otsdb_status otsdb_agg_run_multi_device(otsdb_ctx* c,
+                                        const otsdb_query_spec* spec,
+                                        int32_t n_out, const int32_t* agg_ids,
+                                        const int32_t* interps,
+                                        const otsdb_batch* b,
+                                        otsdb_result* outs, void* hip_stream) {
+  if (!c || !spec || !b || !outs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  const MultiReq q{n_out, agg_ids, interps, outs};
+  otsdb_status rc = check_multi(spec, q);
+  if (rc) return rc;
+  CtxLock lk(c);
+  HIP_TRY(hipSetDevice(c->device));
+  StreamBinding bind(c, hip_stream);
+  std::vector<int64_t> goff;
+  rc = read_goff(c, b, true, goff);
+  if (!rc) rc = run_multi_impl(c, spec, q, b, goff);
+  return rc;
+}
+
+otsdb_status otsdb_agg_run_multi(otsdb_ctx* c, const otsdb_query_spec* spec,
+                                 int32_t n_out, const int32_t* agg_ids,
+                                 const int32_t* interps, const otsdb_batch* b,
+                                 otsdb_result* outs) {
+  if (!c || !spec || !b || !outs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  const MultiReq q{n_out, agg_ids, interps, outs};
+  const otsdb_status rc = check_multi(spec, q);
+  if (rc) return rc;
+  return run_host(c, spec, b, n_out, outs, &q);
+}
+
+otsdb_status otsdb_agg_run_cells_multi_device(
+    otsdb_ctx* c, const otsdb_query_spec* spec, int32_t n_out,
+    const int32_t* agg_ids, const int32_t* interps, const otsdb_cells* cells,
+    const otsdb_batch* b, otsdb_result* outs, void* hip_stream) {
+  if (!c || !spec || !cells || !b || !outs)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  const MultiReq q{n_out, agg_ids, interps, outs};
+  otsdb_status rc = check_multi(spec, q);
+  if (rc) return rc;
+  CtxLock lk(c);
+  HIP_TRY(hipSetDevice(c->device));
+  StreamBinding bind(c, hip_stream);
+  std::vector<int64_t> goff;
+  rc = read_goff(c, b, true, goff);
+  if (rc) return rc;
+  const otsdb_query_spec s0 = multi_spec(spec, q, 0);
+  c->multi_failed = -1;
+  if (n_out == 1) {  // the single query, unchanged
+    c->n_multi_ds = c->n_multi_group = 1;
+    c->n_multi_kt = c->n_multi_tf = 0;
+    return run_cells_impl(c, &s0, cells, b, &outs[0], goff);
+  }
+  return run_cells_impl(c, &s0, cells, b, nullptr, goff, &q);
 }
 
 }  // extern "C"
@@ -3541,9 +4251,11 @@ otsdb_status otsdb_prof_read(otsdb_ctx* c, double* ms, int64_t* launches,
 otsdb_status otsdb_ctx_counters(otsdb_ctx* c, int64_t* out, int n) {
   if (!c || (n > 0 && !out)) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
   CtxLock lk(c);
-  const int64_t v[5] = {c->n_cells_uniform, c->n_cells_general,
-                        c->n_cells_uni_miss, c->sel.key_reads, c->sel.passes};
-  for (int i = 0; i < n && i < 5; ++i) out[i] = v[i];
+  const int64_t v[9] = {c->n_cells_uniform, c->n_cells_general,
+                        c->n_cells_uni_miss, c->sel.key_reads, c->sel.passes,
+                        c->n_multi_ds,       c->n_multi_group, c->n_multi_kt,
+                        c->n_multi_tf};
+  for (int i = 0; i < n && i < 9; ++i) out[i] = v[i];
   return OTSDB_OK;
 }
 

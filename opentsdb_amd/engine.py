@@ -14,7 +14,8 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .core import (IllegalStateException, NoSuchElementException,
+from .core import (Aggregator, Aggregators, IllegalArgumentException,
+                   IllegalStateException, NoSuchElementException,
                    raise_for_status)
 
 
@@ -98,6 +99,36 @@ class SeekableView:
         self.i = int(np.searchsorted(self.dps.ts, timestamp, side="left"))
 
 
+def multi_args(aggs, interps=None):
+    """The aggregator set of a multi-aggregator call as the C-ABI takes it:
+    (n_out, int32 ids, int32 interpolations).  `aggs`: core.Aggregators
+    entries, names (Aggregators.get: NoSuchElementException) or ids;
+    `interps`: one interpolation per output, None = the aggregator's own.
+    Checked before anything touches the device."""
+    aggs = list(aggs)
+    if not 1 <= len(aggs) <= abi.MULTI_MAX:
+        raise IllegalArgumentException(
+            "%d aggregators: a multi-aggregator call takes 1 to %d"
+            % (len(aggs), abi.MULTI_MAX))
+    ids = np.empty(len(aggs), np.int32)
+    for i, a in enumerate(aggs):
+        if isinstance(a, str):
+            a = Aggregators.get(a)
+        ids[i] = a.id if isinstance(a, Aggregator) else int(a)
+    if interps is None:
+        it = np.full(len(aggs), -1, np.int32)
+    else:
+        interps = list(interps)
+        if len(interps) != len(aggs):
+            raise IllegalArgumentException(
+                "%d interpolations for %d aggregators"
+                % (len(interps), len(aggs)))
+        it = np.array([-1 if v is None else int(v) for v in interps], np.int32)
+        if ((it < -1) | (it > 4)).any():
+            raise IllegalArgumentException("bad interpolation in %r" % (interps,))
+    return len(aggs), ids, it
+
+
 class Engine:
     """One context per GPU (one process per GPU)."""
 
@@ -116,6 +147,17 @@ class Engine:
         return dict(cells_uniform=out[0], cells_general=out[1],
                     cells_uniform_miss=out[2], sel_key_reads=out[3],
                     sel_passes=out[4])
+
+    def multi_counters(self):
+        """Of the last multi-aggregator call (otsdb_ctx_counters [5..8]):
+        downsample passes over the point stream, group-stage passes over a
+        row matrix, key transposes, transform passes (one per interpolation
+        class).  A call that cannot share the rows runs its outputs as single
+        queries: downsample and group passes then count those."""
+        out = (C.c_int64 * 9)()
+        self._check(self.lib.otsdb_ctx_counters(self.ctx, out, 9))
+        return dict(downsample_passes=out[5], group_passes=out[6],
+                    key_transposes=out[7], transform_passes=out[8])
 
     def close(self):
         if self.ctx:
@@ -156,6 +198,41 @@ class Engine:
                                            C.byref(r)))
         return [DataPoints(ts[offs[g]:offs[g + 1]], bits[offs[g]:offs[g + 1]],
                            isint[offs[g]:offs[g + 1]]) for g in range(G)]
+
+
+    def plan_multi(self, spec, aggs, batch, interps=None):
+        n, ids, it = multi_args(aggs, interps)
+        sz = abi.Sizes()
+        self._check(self.lib.otsdb_agg_plan_multi(
+            self.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
+            C.byref(batch.as_abi()), C.byref(sz)))
+        return sz
+
+    def run_multi(self, spec, aggs, batch, interps=None):
+        """Several cross-series aggregators over one downsample pass of the
+        same query (host arrays): `spec` with its aggregator replaced by each
+        of `aggs` in turn.  Returns one list of DataPoints (one per group)
+        per aggregator, each what run() gives for that aggregator."""
+        n, ids, it = multi_args(aggs, interps)
+        sz = self.plan_multi(spec, ids, batch, it)
+        cap = max(1, int(sz.max_out_points))
+        G = batch.n_groups
+        offs = np.zeros((n, G + 1), np.int64)
+        ts = np.zeros((n, cap), np.int64)
+        bits = np.zeros((n, cap), np.int64)
+        isint = np.zeros((n, cap), np.uint8)
+        rs = (abi.Result * n)()
+        for i in range(n):
+            rs[i] = abi.Result(cap, offs[i].ctypes.data, ts[i].ctypes.data,
+                               bits[i].ctypes.data, isint[i].ctypes.data)
+        b = batch.as_abi()
+        self._check(self.lib.otsdb_agg_run_multi(
+            self.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
+            C.byref(b), rs))
+        return [[DataPoints(ts[i, offs[i, g]:offs[i, g + 1]],
+                            bits[i, offs[i, g]:offs[i, g + 1]],
+                            isint[i, offs[i, g]:offs[i, g + 1]])
+                 for g in range(G)] for i in range(n)]
 
 
 class DeviceBatch:
@@ -266,3 +343,22 @@ def run_device(engine, spec, dbatch, dresult, stream=None):
     engine._check(engine.lib.otsdb_agg_run_device(
         engine.ctx, C.byref(spec), C.byref(b), C.byref(r),
         None if stream is None else C.c_void_p(stream)))
+
+
+def run_multi_device(engine, spec, aggs, dbatch, dresults, stream=None,
+                     interps=None):
+    """Device-resident multi-aggregator call: dresults[i] (a DeviceResult)
+    takes what run_device gives for aggs[i]; the point stream is downsampled
+    once for all of them."""
+    n, ids, it = multi_args(aggs, interps)
+    if len(dresults) != n:
+        raise IllegalArgumentException(
+            "%d results for %d aggregators" % (len(dresults), n))
+    b = _abi_cached(dbatch, _BATCH_TENSORS, dbatch.as_abi,
+                    dbatch.group_offsets._version)
+    rs = (abi.Result * n)()
+    for i, r in enumerate(dresults):
+        rs[i] = _abi_cached(r, _RESULT_TENSORS, r.as_abi, r.cap)
+    engine._check(engine.lib.otsdb_agg_run_multi_device(
+        engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
+        C.byref(b), rs, None if stream is None else C.c_void_p(stream)))

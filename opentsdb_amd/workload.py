@@ -262,3 +262,28 @@ def run_cells_device(engine, spec, cells, db_groups, result):
     r = result.as_abi()
     engine._check(engine.lib.otsdb_agg_run_cells_device(
         engine.ctx, C.byref(spec), C.byref(c), C.byref(b), C.byref(r), None))
+
+
+def run_cells_multi_device(engine, spec, aggs, cells, db_groups, results,
+                           interps=None):
+    """otsdb_agg_run_cells_multi_device: several aggregators over one decode
+    + downsample of the compacted columns; results[i] takes aggs[i]'s."""
+    import ctypes as C
+    from .engine import multi_args
+    n, ids, it = multi_args(aggs, interps)
+    if len(results) != n:
+        raise core.IllegalArgumentException(
+            "%d results for %d aggregators" % (len(results), n))
+    b = abi.Batch()
+    b.n_series = cells.n_series
+    b.n_points = 0
+    b.n_groups = db_groups.n_groups
+    b.group_offsets = db_groups.group_offsets.data_ptr()
+    b.group_members = db_groups.group_members.data_ptr()
+    c = cells.as_abi()
+    rs = (abi.Result * n)()
+    for i, r in enumerate(results):
+        rs[i] = r.as_abi()
+    engine._check(engine.lib.otsdb_agg_run_cells_multi_device(
+        engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
+        C.byref(c), C.byref(b), rs, None))
