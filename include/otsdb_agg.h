@@ -365,6 +365,54 @@ otsdb_status otsdb_agg_finalize_device(otsdb_ctx* ctx,
                                        const uint8_t* emit,
                                        otsdb_result* out, void* hip_stream);
 
+/* ---- several aggregators across ranks: shared partials ------------------ */
+/* The multi-aggregator call (otsdb_agg_run_multi*) over series-sharded
+ * ranks: the spans of one group (TsdbQuery.java:992-1113 builds one
+ * SpanGroup per aggregator of a panel over the same spans) are spread over
+ * GPUs.  Each rank downsamples its shard ONCE and writes, for every output
+ * i, one partial per (group, bucket) into partials[i][G*n_buckets] (DEVICE,
+ * output-major) plus ONE emit mask for all outputs: a (group, bucket) is
+ * emitted iff some member has a real point in it
+ * (AggregationIterator.java:514-567), whatever the aggregator, so the mask
+ * does not depend on the output.  agg_ids / interps and their checks are
+ * otsdb_agg_run_multi_device's.  Slice i of `partials` with `emit` is what
+ * otsdb_agg_partials_device writes for aggregator i up to the order of the
+ * local reduction (and a valid input of otsdb_agg_finalize_device).  Scalar
+ * aggregators share one group pass; `dev` takes its own pass over the shared
+ * rows and its per-rank states are merged by Chan's formula (handing states
+ * on from rank to rank stays with otsdb_agg_partials_chained_device).
+ * Median / p* / ep* are refused with OTSDB_E_ILLEGAL_ARGUMENT: they take the
+ * otsdb_sel_* protocol (otsdb_sel_retarget for several of them).  What
+ * otsdb_agg_partials_device refuses (raw group-by, per-series calendar
+ * anchors, grids past 4e9 cells): OTSDB_E_UNSUPPORTED.  n_out == 1 and
+ * queries whose outputs cannot share the rows run the outputs one after
+ * another: same results, otsdb_ctx_counters [5] == n_out.                   */
+otsdb_status otsdb_agg_partials_multi_device(otsdb_ctx* ctx,
+                                             const otsdb_query_spec* spec,
+                                             int32_t n_out,
+                                             const int32_t* agg_ids,
+                                             const int32_t* interps,
+                                             const otsdb_batch* batch,
+                                             otsdb_partial* partials,
+                                             uint8_t* emit, void* hip_stream);
+/* Combines the ranks' partial sets, DEVICE [n_ranks][n_out][G*n_buckets]
+ * with emit [n_ranks][G*n_buckets], in rank order (= series order) and
+ * writes output i into outs[i] (HOST array of n_out structs, DEVICE pointers
+ * inside): bit for bit what otsdb_agg_finalize_device gives for slice i.
+ * Returns the status of the lowest-index failing output.                    */
+otsdb_status otsdb_agg_finalize_multi_device(otsdb_ctx* ctx,
+                                             const otsdb_query_spec* spec,
+                                             int32_t n_out,
+                                             const int32_t* agg_ids,
+                                             const int32_t* interps,
+                                             int64_t n_groups,
+                                             int64_t n_buckets,
+                                             int32_t n_ranks,
+                                             const otsdb_partial* partials,
+                                             const uint8_t* emit,
+                                             otsdb_result* outs,
+                                             void* hip_stream);
+
 /* ---- multi-GPU median / percentiles (series-sharded) -------------------- */
 /* Exact selection across ranks: digit histograms summed over
  * the ranks, at most two passes over each rank's local keys.  The protocol,
@@ -403,9 +451,29 @@ otsdb_status otsdb_agg_finalize_device(otsdb_ctx* ctx,
  * Every rank ends with the full result.  The batch's group_offsets span all
  * G global groups (empty where the rank holds no member).  Between prepare
  * and finish the context must not run other queries (the session lives in
- * its workspace).  Replaces PercentileAgg/Median.runDouble over the spans of
+ * its workspace): every other entry that takes the context (run*,
+ * partials*, finalize*, decode, ...; not plan, the counters or the
+ * profiling reads) ENDS the session, and the next otsdb_sel_* call other
+ * than prepare returns OTSDB_E_ILLEGAL_STATE instead of reading overwritten
+ * keys.  Replaces PercentileAgg/Median.runDouble over the spans of
  * a group (Aggregators.java:397-431, :657-708) when the spans are spread
- * over GPUs.                                                               */
+ * over GPUs.
+ *
+ * Several percentiles of one panel (p99 + p999: one PercentileAgg per
+ * sub-query over the same spans, Aggregators.java:657-708):
+ *
+ *   otsdb_sel_retarget(ctx, agg_id)
+ *       legal while a session exists: after a successful prepare, also after
+ *       finish.  Re-aims the session at another median / p* / ep* and resets
+ *       its pass state; the caller runs hist (pass 0 with the SAME already
+ *       all-reduced counts / emit / krange), pick and finish again.  No new
+ *       prepare, downsample or key transpose and no new all-reduce of counts
+ *       / emit / krange: the local keys and those three do not depend on the
+ *       percentile.  Not a selection, or one whose own interpolation differs
+ *       from the prepared aggregator's while the spec leaves the
+ *       interpolation to the aggregator and has no fill policy (the prepared
+ *       contributions would differ): OTSDB_E_ILLEGAL_ARGUMENT; no session:
+ *       OTSDB_E_ILLEGAL_STATE.                                              */
 #define OTSDB_SEL_BINS 2048
 otsdb_status otsdb_sel_prepare_device(otsdb_ctx* ctx,
                                       const otsdb_query_spec* spec,
@@ -421,6 +489,7 @@ otsdb_status otsdb_sel_pick_device(otsdb_ctx* ctx, int64_t* picks,
                                    void* hip_stream);
 otsdb_status otsdb_sel_finish_device(otsdb_ctx* ctx, const int64_t* picks,
                                      otsdb_result* out, void* hip_stream);
+otsdb_status otsdb_sel_retarget(otsdb_ctx* ctx, int32_t agg_id);
 /* Blocks until the kernels otsdb_sel_hist_device / _pick_device enqueued on
  * hip_stream (NULL: the context's stream) are done.                         */
 otsdb_status otsdb_sel_hist_wait(otsdb_ctx* ctx, void* hip_stream);
@@ -602,7 +671,8 @@ otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
  * session.  Of the last otsdb_agg_*_multi* call: out[5] downsample
  * (bucketize) passes over the point stream, out[6] group-stage passes over
  * a row matrix, out[7] key transposes, out[8] transform passes (one per
- * interpolation class).                                                    */
+ * interpolation class).  out[9]: otsdb_sel_* sessions prepared since the
+ * context was created (otsdb_sel_retarget prepares none).                  */
 otsdb_status otsdb_ctx_counters(otsdb_ctx* ctx, int64_t* out, int n);
 /* Test hook: the one-pass compaction's epoch (1 .. 2^24 - 1, forward only)
  * the context's next call increments, so tests can drive it to its wrap.  */

@@ -152,6 +152,8 @@ EXPORTS = [
     "otsdb_agg_run_raw_device", "otsdb_agg_run_raw", "otsdb_agg_run_cells",
     "otsdb_agg_plan_multi", "otsdb_agg_run_multi_device",
     "otsdb_agg_run_multi", "otsdb_agg_run_cells_multi_device",
+    "otsdb_agg_partials_multi_device", "otsdb_agg_finalize_multi_device",
+    "otsdb_sel_retarget",
 ]
 
 MULTI_MAX = 32  # OTSDB_MULTI_MAX
@@ -256,6 +258,20 @@ def load(path=None):
     lib.otsdb_agg_run_cells_multi_device.argtypes = [vp, PS, i32, vp, vp, PC,
                                                      PB, PR, vp]
     lib.otsdb_agg_run_cells_multi_device.restype = C.c_int
+    # the same across ranks: (ctx, spec, n_out, agg_ids, interps, batch,
+    # partials[n_out][GB], emit[GB], stream) and (ctx, spec, n_out, agg_ids,
+    # interps, G, n_buckets, n_ranks, partials, emit, results[n_out], stream)
+    lib.otsdb_agg_partials_multi_device.argtypes = [vp, PS, i32, vp, vp, PB,
+                                                    vp, vp, vp]
+    lib.otsdb_agg_partials_multi_device.restype = C.c_int
+    lib.otsdb_agg_finalize_multi_device.argtypes = [vp, PS, i32, vp, vp, i64,
+                                                    i64, i32, vp, vp, PR, vp]
+    lib.otsdb_agg_finalize_multi_device.restype = C.c_int
+    # bound only on the ABI it was added to: a stale library of another
+    # version must not hand out a symbol of other arguments
+    if lib.otsdb_abi_version() == 6 and hasattr(lib, "otsdb_sel_retarget"):
+        lib.otsdb_sel_retarget.argtypes = [vp, i32]
+        lib.otsdb_sel_retarget.restype = C.c_int
     lib.otsdb_prof_enable.argtypes = [vp, C.c_int]
     lib.otsdb_prof_enable.restype = C.c_int
     lib.otsdb_prof_read.argtypes = [vp, vp, vp, C.c_int, C.c_int]

@@ -307,6 +307,7 @@ struct otsdb_ctx {
     // diagnostics (otsdb_ctx_counters): passes over the local key matrix
     // and histogram passes of the last session
     int64_t key_reads = 0, passes = 0;
+    int64_t sessions = 0;  // prepared since the context was created ([9])
     void* pool = nullptr;    // candidates: keys [cap] | segments [cap]
     size_t pool_bytes = 0;
     int64_t pool_cap = 0;
@@ -336,11 +337,16 @@ otsdb_status ensure(void** p, size_t* cap, size_t need) {
 // mark for this call (clean_entry) and clears it: only the one-pass
 // compaction's read-back (finish) sets it again, after k_compact1 zeroed
 // the word — any other call may leave bits in it.
+// A cross-rank selection session lives in the workspace the other entries
+// overwrite: every call ends it, except the session's own entries and the
+// diagnostics (keep_session), so that a late otsdb_sel_* call reports
+// E_ILLEGAL_STATE instead of reading another query's bytes.
 struct CtxLock {
   std::lock_guard<std::mutex> lk;
-  explicit CtxLock(otsdb_ctx* c) : lk(c->mu) {
+  explicit CtxLock(otsdb_ctx* c, bool keep_session = false) : lk(c->mu) {
     c->clean_entry = c->err_clean;
     c->err_clean = false;
+    if (!keep_session) c->sel.active = false;
   }
 };
 
@@ -2066,12 +2072,15 @@ otsdb_status multi_buffers(otsdb_ctx* c) {
 
 // "Build the rows" once for every output: the tiles, the workspace of the
 // whole call and the downsample pass (fold off: the rows are what is
-// shared).  cells: as run_pipeline's.
+// shared).  cells: as run_pipeline's.  partial: the call leaves partials for
+// the merge across ranks (multi_partials) — dev's chains are those of the
+// single partials entry (kOrderedChunkMerged), its merge covers every group.
 otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
                          const MultiReq& q, const BatchDev& B,
                          const int64_t* d_members, std::vector<int64_t>& goff,
                          const Params& P0, const CellsDev* cells,
-                         const int64_t* series_row, MultiState& M) {
+                         const int64_t* series_row, MultiState& M,
+                         bool partial = false) {
   hipStream_t st = c->stream;
   otsdb_status rc = multi_buffers(c);
   if (rc) return rc;
@@ -2117,7 +2126,8 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
   // dev's own tiles (one chain per group up to kOrderedChunk members): how
   // many groups its merge covers, and its longest
   int64_t mg_dev = 0, max_dev = 0;
-  const int64_t whole = M.exact ? INT64_MAX : kOrderedChunk;
+  const int64_t whole = partial ? kOrderedChunkMerged
+                                : (M.exact ? INT64_MAX : kOrderedChunk);
   M.empty_group = false;
   for (int64_t g = 0; g < G; ++g) {
     const int64_t k = goff[g + 1] - goff[g];
@@ -2127,6 +2137,7 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
       max_dev = std::max(max_dev, (k + kChunk - 1) / kChunk);
     }
   }
+  if (partial) mg_dev = G;  // k_combine packs every group's state
   M.two_level_dev = max_dev > kCombineL1 &&
                     (double)mg_dev * kCombineSlices * NB * 33.0 < 2.0e9;
   const int64_t n_comb = std::max(M.two_level ? T.MG : 0,
@@ -2163,8 +2174,8 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
     W.out_val = cv.take<double>((size_t)G * NB);
     W.out_emit = cv.take<uint8_t>((size_t)G * NB);
     for (int i = 0; i < q.n; ++i) {
-      M.out_val[i] = cv.take<double>((size_t)G * NB);
-      M.out_emit[i] = cv.take<uint8_t>((size_t)G * NB);
+      M.out_val[i] = partial ? nullptr : cv.take<double>((size_t)G * NB);
+      M.out_emit[i] = partial ? nullptr : cv.take<uint8_t>((size_t)G * NB);
     }
     W.counts = nullptr;
     if (n_comb > 0) {
@@ -2189,7 +2200,7 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
   HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(int), st));
   HIP_TRY(hipMemsetAsync(c->d_merr, 0, OTSDB_MULTI_MAX * sizeof(int), st));
   c->clean_entry = false;
-  if (M.empty_group) {
+  if (M.empty_group && !partial) {
     HIP_TRY(hipMemsetAsync(W.out_emit, 0, (size_t)G * NB, st));
     for (int i = 0; i < q.n; ++i)
       HIP_TRY(hipMemsetAsync(M.out_emit[i], 0, (size_t)G * NB, st));
@@ -2200,6 +2211,87 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
   if (rc) return rc;
   ++c->n_multi_ds;
   HIP_TRY(hipGetLastError());
+  return OTSDB_OK;
+}
+
+// Wc: the work set over interpolation class k's matrix — k_transform in
+// place for one class, k_transform_interp into the second matrix for several
+otsdb_status multi_class_rows(otsdb_ctx* c, MultiState& M, int k, Work& Wc) {
+  const int64_t NB = M.NB, S = M.S;
+  Params& P = M.P;
+  Wc = M.W;
+  if (M.n_cls == 1) {
+    P.interp = M.cls_interp[0];
+    transform_rows(c, P, M.B, M.W, M.rate_fused);
+  } else {
+    StageTimer tm(c, 1);
+    Params Pc = P;
+    Pc.interp = M.cls_interp[k];
+    if (!P.sentinel)
+      HIP_TRY(hipMemsetAsync(M.R2.state, 0, (size_t)S * NB, c->stream));
+    hipLaunchKernelGGL(k_transform_interp, dim3(blocks_for(S, 4)), dim3(256),
+                       0, c->stream, Pc, M.B, M.W.SM, M.W.R, M.R2);
+    Wc.R = M.R2;
+  }
+  ++c->n_multi_tf;
+  return OTSDB_OK;
+}
+
+// k_group_multi's request for the scalar, unordered outputs of class k:
+// slots, mask and tile partials (MA.out[j] is the caller's); who[j]: the
+// output behind launch output j
+void multi_scalar_args(const MultiState& M, int k, MultiArgs& MA, int* who) {
+  const MultiReq& q = M.q;
+  for (int i = 0; i < q.n; ++i) {
+    if (M.cls[i] != k || M.kind[i] != MK_SCALAR) continue;
+    const int j = MA.n_out++;
+    who[j] = i;
+    with_monoid(q.aggs[i], [&](auto tag) {
+      MA.slot[j] = MultiSlot<decltype(tag)>::value;
+    });
+    MA.mask |= 1u << (MA.slot[j] & 31);
+  }
+  for (int s = 0; s < kMultiSlots; ++s) MA.partial[s] = M.partial[s];
+}
+
+// Every output through the existing compaction into its own result, one
+// synchronisation, the status of the lowest-index failing output.
+otsdb_status multi_compact_outputs(otsdb_ctx* c, const MultiReq& q,
+                                   const Params& P, int64_t G,
+                                   double* const* out_val,
+                                   uint8_t* const* out_emit) {
+  hipStream_t st = c->stream;
+  otsdb_status rc;
+  for (int i = 0; i < q.n; ++i) {
+    Params Pi = P;
+    agg_params(&Pi, q.aggs[i], q.interps ? q.interps[i] : OTSDB_INTERP_DEFAULT);
+    rc = compact(c, Pi, G, out_val[i], out_emit[i], nullptr, &q.outs[i],
+                 c->d_merr + i, c->d_mdone + 4 * i);
+    if (rc) return rc;
+  }
+  // (the next call of any kind clears the context's word itself: err_clean
+  // stays false, as after a single query that did not end in k_compact1)
+  c->small_ready = false;
+  c->h_small[0] = 0;
+  HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
+                         hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int shared = (int)(c->h_small[0] & 0xFFFFFFFF);
+  for (int i = 0; i < q.n; ++i) {
+    int64_t* d = c->h_mdone + 4 * i;
+    int e = shared | (int)(__atomic_load_n(&d[0], __ATOMIC_ACQUIRE) & 0xFFFFFFFF);
+    c->multi_total[i] = __atomic_load_n(&d[1], __ATOMIC_ACQUIRE);
+    if (__atomic_load_n(&d[2], __ATOMIC_ACQUIRE)) {
+      d[2] = 0;
+      e |= ERR_INTERNAL;
+    }
+    rc = result_status(e, c->multi_total[i], q.outs[i].capacity);
+    if (rc) {
+      c->multi_failed = i;
+      if (rc == OTSDB_E_CAPACITY) c->result_short = true;
+      return rc;
+    }
+  }
   return OTSDB_OK;
 }
 
@@ -2239,20 +2331,9 @@ otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M) {
     }
   }
   for (int k = 0; k < M.n_cls && !M.sel_fused; ++k) {
-    Work Wc = M.W;  // this class's matrix
-    if (M.n_cls == 1) {
-      P.interp = M.cls_interp[0];
-      transform_rows(c, P, M.B, M.W, M.rate_fused);
-    } else {
-      StageTimer tm(c, 1);
-      Params Pc = P;
-      Pc.interp = M.cls_interp[k];
-      if (!P.sentinel) HIP_TRY(hipMemsetAsync(M.R2.state, 0, (size_t)S * NB, st));
-      hipLaunchKernelGGL(k_transform_interp, dim3(blocks_for(S, 4)), dim3(256),
-                         0, st, Pc, M.B, M.W.SM, M.W.R, M.R2);
-      Wc.R = M.R2;
-    }
-    ++c->n_multi_tf;
+    Work Wc;  // this class's matrix
+    rc = multi_class_rows(c, M, k, Wc);
+    if (rc) return rc;
     StageTimer tm(c, 2);
     rc = build_tiles(c, *M.goff, false, M.chunk, M.whole);  // (cached unless dev ran)
     if (rc) return rc;
@@ -2261,19 +2342,12 @@ otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M) {
     // ---- the scalar, unordered outputs: one pass for all of them
     MultiArgs MA{};
     int who[OTSDB_MULTI_MAX];
-    for (int i = 0; i < q.n; ++i) {
-      if (M.cls[i] != k || M.kind[i] != MK_SCALAR) continue;
-      const int j = MA.n_out++;
-      who[j] = i;
-      with_monoid(q.aggs[i], [&](auto tag) {
-        MA.slot[j] = MultiSlot<decltype(tag)>::value;
-      });
-      MA.mask |= 1u << (MA.slot[j] & 31);
-      MA.out[j] = MultiOut{M.out_val[i], M.out_emit[i], c->d_merr + i};
-    }
-    for (int s = 0; s < kMultiSlots; ++s) MA.partial[s] = M.partial[s];
+    multi_scalar_args(M, k, MA, who);
+    for (int j = 0; j < MA.n_out; ++j)
+      MA.out[j] = MultiOut{M.out_val[who[j]], M.out_emit[who[j]],
+                           c->d_merr + who[j], nullptr};
     if (MA.n_out > 0 && T.T > 0) {
-      hipLaunchKernelGGL(k_group_multi, dim3(blocks_for(T.T * NB, 256)),
+      hipLaunchKernelGGL(k_group_multi<false>, dim3(blocks_for(T.T * NB, 256)),
                          dim3(256), 0, st, NB, T.T, T.tg, T.tm0, T.tm1,
                          T.single, M.d_members, Wc.R, M.W.tile_emit, MA);
       ++c->n_multi_group;
@@ -2340,37 +2414,73 @@ otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M) {
     }
   }
   HIP_TRY(hipGetLastError());
-  // ---- every output through the existing compaction into its own result
-  for (int i = 0; i < q.n; ++i) {
-    Params Pi = P;
-    agg_params(&Pi, q.aggs[i], q.interps ? q.interps[i] : OTSDB_INTERP_DEFAULT);
-    rc = compact(c, Pi, G, M.out_val[i], M.out_emit[i], nullptr, &q.outs[i],
-                 c->d_merr + i, c->d_mdone + 4 * i);
+  return multi_compact_outputs(c, q, P, G, M.out_val, M.out_emit);
+}
+
+// multi_aggregate's partial-emitting form (otsdb_agg_partials_multi_device):
+// output i's per-(group, bucket) states into partials[i][G * NB], one emit
+// mask for all outputs.  Scalar outputs: one k_group_multi<PARTIAL> launch
+// per class, groups of several tiles through k_combine<M>'s packing form,
+// groups without a local member the monoid's identity; dev: k_group<MDev>
+// over the single partials entry's tiles, every group through k_combine.
+otsdb_status multi_partials(otsdb_ctx* c, MultiState& M, Packed* partials,
+                            uint8_t* emit) {
+  hipStream_t st = c->stream;
+  const MultiReq& q = M.q;
+  const int64_t G = M.G, NB = M.NB, GB = G * NB;
+  otsdb_status rc;
+  for (int k = 0; k < M.n_cls; ++k) {
+    Work Wc;
+    rc = multi_class_rows(c, M, k, Wc);
     if (rc) return rc;
-  }
-  // (the next call of any kind clears the context's word itself: err_clean
-  // stays false, as after a single query that did not end in k_compact1)
-  c->small_ready = false;
-  c->h_small[0] = 0;
-  HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
-                         hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const int shared = (int)(c->h_small[0] & 0xFFFFFFFF);
-  for (int i = 0; i < q.n; ++i) {
-    int64_t* d = c->h_mdone + 4 * i;
-    int e = shared | (int)(__atomic_load_n(&d[0], __ATOMIC_ACQUIRE) & 0xFFFFFFFF);
-    c->multi_total[i] = __atomic_load_n(&d[1], __ATOMIC_ACQUIRE);
-    if (__atomic_load_n(&d[2], __ATOMIC_ACQUIRE)) {
-      d[2] = 0;
-      e |= ERR_INTERNAL;
+    StageTimer tm(c, 2);
+    rc = build_tiles(c, *M.goff, false, M.chunk, M.whole);  // (cached unless dev ran)
+    if (rc) return rc;
+    const Tiles T = tiles_of(c, G);
+    MultiArgs MA{};
+    int who[OTSDB_MULTI_MAX];
+    multi_scalar_args(M, k, MA, who);
+    for (int j = 0; j < MA.n_out; ++j)
+      MA.out[j] = MultiOut{nullptr, emit, c->d_merr + who[j],
+                           partials + (size_t)who[j] * GB};
+    if (MA.n_out > 0) {
+      if (T.T > 0)
+        hipLaunchKernelGGL(k_group_multi<true>, dim3(blocks_for(T.T * NB, 256)),
+                           dim3(256), 0, st, NB, T.T, T.tg, T.tm0, T.tm1,
+                           T.single, M.d_members, Wc.R, M.W.tile_emit, MA);
+      ++c->n_multi_group;
+      if (T.MG > 0)
+        for (int j = 0; j < MA.n_out; ++j) {
+          Work Ws = Wc;
+          Ws.partial = M.partial[MA.slot[j]];
+          with_monoid(q.aggs[who[j]], [&](auto tag) {
+            launch_combine<decltype(tag)>(c, Ws, NB, T.MG, T.mg, T.mt0, T.mt1,
+                                          nullptr, emit, MA.out[j].part,
+                                          M.two_level, 0, c->d_merr + who[j]);
+          });
+        }
+      if (M.empty_group)
+        hipLaunchKernelGGL(k_partial_empty_multi, dim3(blocks_for(GB, 256)),
+                           dim3(256), 0, st, NB, G, T.at0, T.at1, MA);
     }
-    rc = result_status(e, c->multi_total[i], q.outs[i].capacity);
-    if (rc) {
-      c->multi_failed = i;
-      if (rc == OTSDB_E_CAPACITY) c->result_short = true;
-      return rc;
+    bool dev_tiles = false;
+    for (int i = 0; i < q.n; ++i) {
+      if (M.cls[i] != k || M.kind[i] != MK_ORDERED) continue;
+      if (!dev_tiles) {
+        rc = build_tiles(c, *M.goff, false, kChunk, kOrderedChunkMerged);
+        if (rc) return rc;
+        dev_tiles = true;
+      }
+      const Tiles Td = tiles_of(c, G);
+      const AggStage Ad{M.d_members, M.goff->back(), 1,       false,
+                        M.two_level_dev,
+                        partials + (size_t)i * GB, emit, nullptr, nullptr};
+      rc = group_rows(c, q.aggs[i], Wc, Td, NB, G, Ad, c->d_merr + i);
+      if (rc) return rc;
+      ++c->n_multi_group;
     }
   }
+  HIP_TRY(hipGetLastError());
   return OTSDB_OK;
 }
 
@@ -3508,25 +3618,28 @@ otsdb_status otsdb_agg_run_cells_multi_device(
 }  // extern "C"
 
 namespace {
-otsdb_status partials_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                           const otsdb_batch* b, const otsdb_partial* init,
-                           const uint8_t* init_emit, otsdb_partial* partials,
-                           uint8_t* emit, void* hip_stream) {
-  if (!c || !spec || !b || !partials || !emit || (!init != !init_emit))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  StreamBinding bind(c, hip_stream);
-  std::vector<int64_t> goff;
-  otsdb_status rc = read_goff(c, b, true, goff);
-  Params P;
-  if (!rc) rc = check_spec(spec);
-  if (!rc) rc = make_params(spec, &P, c);
+// what no partials entry takes: the grid of a query the ranks cannot merge
+otsdb_status partials_grid(otsdb_ctx* c, const otsdb_query_spec* spec,
+                           const otsdb_batch* b, Params* P) {
+  otsdb_status rc = check_spec(spec);
+  if (!rc) rc = make_params(spec, P, c);
   if (!rc && !(spec->ds_interval_ms > 0 || spec->run_all))
     rc = fail(OTSDB_E_UNSUPPORTED,
               "raw group-by across ranks (union timestamps need an all-gather)");
-  if (!rc && !P.run_all && !P.fill && (double)b->n_series * (double)P.nb > 4.0e9)
+  if (!rc && !P->run_all && !P->fill &&
+      (double)b->n_series * (double)P->nb > 4.0e9)
     rc = fail(OTSDB_E_UNSUPPORTED, "grid trimming is not supported across ranks");
+  return rc;
+}
+
+// one aggregator's partials (the context locked, the stream bound)
+otsdb_status partials_locked(otsdb_ctx* c, const otsdb_query_spec* spec,
+                             const otsdb_batch* b, std::vector<int64_t>& goff,
+                             const otsdb_partial* init,
+                             const uint8_t* init_emit, otsdb_partial* partials,
+                             uint8_t* emit) {
+  Params P;
+  otsdb_status rc = partials_grid(c, spec, b, &P);
   if (!rc) {
     BatchDev B{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
                b->series_float};
@@ -3561,9 +3674,167 @@ otsdb_status partials_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   }
   return rc;
 }
+
+otsdb_status partials_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
+                           const otsdb_batch* b, const otsdb_partial* init,
+                           const uint8_t* init_emit, otsdb_partial* partials,
+                           uint8_t* emit, void* hip_stream) {
+  if (!c || !spec || !b || !partials || !emit || (!init != !init_emit))
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  CtxLock lk(c);
+  HIP_TRY(hipSetDevice(c->device));
+  StreamBinding bind(c, hip_stream);
+  std::vector<int64_t> goff;
+  otsdb_status rc = read_goff(c, b, true, goff);
+  if (!rc) rc = partials_locked(c, spec, b, goff, init, init_emit, partials, emit);
+  return rc;
+}
+
+// the multi_request checks of the entries that exchange partials: the
+// selections take the otsdb_sel_* protocol
+otsdb_status check_multi_partials(const otsdb_query_spec* spec,
+                                  const MultiReq& q) {
+  const otsdb_status rc = check_multi(spec, q);
+  if (rc) return rc;
+  for (int i = 0; i < q.n; ++i)
+    if (is_selection(q.aggs[i]))
+      return fail(OTSDB_E_ILLEGAL_ARGUMENT,
+                  "percentiles across ranks: use the otsdb_sel_* protocol "
+                  "(otsdb_sel_retarget for several)");
+  return OTSDB_OK;
+}
 }  // namespace
 
 extern "C" {
+
+otsdb_status otsdb_agg_partials_multi_device(
+    otsdb_ctx* c, const otsdb_query_spec* spec, int32_t n_out,
+    const int32_t* agg_ids, const int32_t* interps, const otsdb_batch* b,
+    otsdb_partial* partials, uint8_t* emit, void* hip_stream) {
+  if (!c || !spec || !b || !partials || !emit)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  const MultiReq q{n_out, agg_ids, interps, nullptr};
+  otsdb_status rc = check_multi_partials(spec, q);
+  if (rc) return rc;
+  CtxLock lk(c);
+  HIP_TRY(hipSetDevice(c->device));
+  StreamBinding bind(c, hip_stream);
+  std::vector<int64_t> goff;
+  rc = read_goff(c, b, true, goff);
+  if (rc) return rc;
+  const otsdb_query_spec s0 = multi_spec(spec, q, 0);
+  Params P;
+  rc = partials_grid(c, &s0, b, &P);
+  if (rc) return rc;
+  c->multi_failed = -1;
+  c->n_multi_ds = c->n_multi_group = c->n_multi_kt = c->n_multi_tf = 0;
+  const int64_t G = (int64_t)goff.size() - 1;
+  const size_t GB = (size_t)G * P.nb;
+  // (a misaligned batch: the single path reports it)
+  if (((((uintptr_t)b->ts_ms) | ((uintptr_t)b->val)) & 15) ||
+      !multi_shares_rows(spec, q, P, b->n_series, goff)) {
+    // the outputs one after another through the single entry's path: every
+    // one writes the same emit mask
+    for (int i = 0; i < q.n; ++i) {
+      const otsdb_query_spec si = multi_spec(spec, q, i);
+      rc = partials_locked(c, &si, b, goff, nullptr, nullptr,
+                           partials + (size_t)i * GB, emit);
+      if (rc) {
+        c->multi_failed = i;
+        return rc;
+      }
+      ++c->n_multi_ds;
+      ++c->n_multi_group;
+    }
+    return OTSDB_OK;
+  }
+  for (int i = 0; i < q.n; ++i)
+    if (multi_kind(q.aggs[i]) == MK_ORDERED &&
+        (spec->flags & OTSDB_SPEC_EXACT_ORDER))
+      return fail(OTSDB_E_UNSUPPORTED,
+                  "exact-order dev across ranks: hand the chains on "
+                  "(otsdb_agg_partials_chained_device)");
+  BatchDev B{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
+             b->series_float};
+  MultiState M;
+  rc = multi_build(c, &s0, q, B, b->group_members, goff, P, nullptr, nullptr, M,
+                   /*partial=*/true);
+  if (!rc) rc = multi_partials(c, M, (Packed*)partials, emit);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if ((int)(c->h_small[0] & 0xFFFFFFFF) & ERR_RATE_TS)
+    return fail(OTSDB_E_ILLEGAL_STATE,
+                "Next timestamp is supposed to be strictly greater");
+  return OTSDB_OK;
+}
+
+otsdb_status otsdb_agg_finalize_multi_device(
+    otsdb_ctx* c, const otsdb_query_spec* spec, int32_t n_out,
+    const int32_t* agg_ids, const int32_t* interps, int64_t n_groups,
+    int64_t n_buckets, int32_t n_ranks, const otsdb_partial* partials,
+    const uint8_t* emit, otsdb_result* outs, void* hip_stream) {
+  if (!c || !spec || !outs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  const MultiReq q{n_out, agg_ids, interps, outs};
+  otsdb_status rc = check_multi_partials(spec, q);
+  if (rc) return rc;
+  if (n_groups < 0 || n_ranks < 1)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "%lld groups of %d ranks",
+                (long long)n_groups, (int)n_ranks);
+  CtxLock lk(c);
+  HIP_TRY(hipSetDevice(c->device));
+  StreamBinding bind(c, hip_stream);
+  const otsdb_query_spec s0 = multi_spec(spec, q, 0);
+  Params P;
+  rc = make_params(&s0, &P, c);
+  if (!rc && P.nb != n_buckets)
+    rc = fail(OTSDB_E_ILLEGAL_ARGUMENT, "n_buckets %lld != plan %lld",
+              (long long)n_buckets, (long long)P.nb);
+  if (!rc && n_groups * P.nb > 0 && (!partials || !emit))
+    rc = fail(OTSDB_E_ILLEGAL_ARGUMENT, "null partials");
+  if (!rc) rc = multi_buffers(c);
+  if (rc) return rc;
+  c->multi_failed = -1;
+  const int64_t G = n_groups, GB = G * P.nb;
+  FinalizeArgs A{};
+  A.n_out = q.n;
+  double* out_val[OTSDB_MULTI_MAX];
+  uint8_t* out_emit[OTSDB_MULTI_MAX];
+  auto carve = [&](char* base) {
+    Carve cv{base};
+    for (int i = 0; i < q.n; ++i) {
+      out_val[i] = cv.take<double>(GB + 1);
+      out_emit[i] = cv.take<uint8_t>(GB + 1);
+    }
+    return cv.off + 256;
+  };
+  rc = ensure(&c->ws, &c->ws_cap, carve(nullptr));
+  if (rc) return rc;
+  carve((char*)c->ws);
+  for (int i = 0; i < q.n; ++i) {
+    A.slot[i] = kMultiSlotDev;  // (ordered: dev)
+    with_monoid(q.aggs[i], [&](auto tag) {
+      constexpr int k = MultiSlot<decltype(tag)>::value;
+      if (k >= 0) A.slot[i] = k;
+    });
+    A.out[i] = MultiOut{out_val[i], out_emit[i], c->d_merr + i, nullptr};
+  }
+  HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(int), c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_merr, 0, OTSDB_MULTI_MAX * sizeof(int), c->stream));
+  if (GB == 0) {  // no group or no bucket: empty results (compact's zeroes)
+    for (int i = 0; i < q.n && !rc; ++i)
+      rc = compact(c, P, G, out_val[i], out_emit[i], nullptr, &q.outs[i]);
+    c->small_ready = false;
+    if (!rc) HIP_TRY(hipStreamSynchronize(c->stream));
+    return rc;
+  }
+  hipLaunchKernelGGL(k_finalize_ranks_multi, dim3(blocks_for(GB, 256)),
+                     dim3(256), 0, c->stream, GB, (int)n_ranks,
+                     (const Packed*)partials, emit, A);
+  HIP_TRY(hipGetLastError());
+  return multi_compact_outputs(c, q, P, G, out_val, out_emit);
+}
 
 otsdb_status otsdb_agg_partials_device(otsdb_ctx* c,
                                        const otsdb_query_spec* spec,
@@ -3704,9 +3975,42 @@ otsdb_status otsdb_sel_prepare_device(otsdb_ctx* c, const otsdb_query_spec* spec
       S.need_pick = false;
       S.key_reads = 0;
       S.passes = 0;
+      ++S.sessions;
     }
   }
   return rc;
+}
+
+// Re-aims the session at another selection aggregator.  What the passes
+// consume is rebuilt by the next pass loop itself: pass 0 rewrites the dense
+// counts (W.out_val, which finish overwrote with values) from the caller's
+// all-reduced counts, the XSel states and the pool bounds; pass 1 the
+// candidate pool.  The keys, their per-tile min / max and W.out_emit are
+// read-only after prepare and stay.
+otsdb_status otsdb_sel_retarget(otsdb_ctx* c, int32_t agg_id) {
+  if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  if (agg_id < 0 || agg_id >= OTSDB_AGG_COUNT_IDS || !is_selection(agg_id))
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT,
+                "otsdb_sel_retarget needs median/percentile, not %d",
+                (int)agg_id);
+  CtxLock lk(c, /*keep_session=*/true);
+  auto& S = c->sel;
+  if (!S.active) return fail(OTSDB_E_ILLEGAL_STATE, "no selection session");
+  if (S.spec.interp == OTSDB_INTERP_DEFAULT && S.spec.fill == OTSDB_FILL_NONE &&
+      kAggs[agg_id].interp != kAggs[S.spec.agg_id].interp)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT,
+                "aggregator %d interpolates unlike the prepared %d",
+                (int)agg_id, (int)S.spec.agg_id);
+  S.spec.agg_id = agg_id;
+  agg_params(&S.P, agg_id, S.spec.interp);
+  S.median = agg_id == OTSDB_AGG_MEDIAN ? 1 : 0;
+  S.next_pass = 0;
+  S.more = false;
+  S.pool_built = false;
+  S.need_pick = false;
+  S.key_reads = 0;
+  S.passes = 0;
+  return OTSDB_OK;
 }
 
 namespace {
@@ -3746,16 +4050,18 @@ otsdb_status otsdb_sel_hist_device(otsdb_ctx* c, int32_t pass,
                                    uint32_t* hist_out, int32_t* more,
                                    void* hip_stream) {
   if (!c || !hist_out || !more) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
+  CtxLock lk(c, /*keep_session=*/true);
   auto& S = c->sel;
   if (!S.active) return fail(OTSDB_E_ILLEGAL_STATE, "no selection session");
-  if (pass != S.next_pass)
+  if (pass < 0 || pass != S.next_pass)
     return fail(OTSDB_E_ILLEGAL_STATE, "pass %d, expected %d", pass, S.next_pass);
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
   const int64_t G = S.G, NB = S.NB, GB = G * NB;
   const Tiles T = tiles_of(c, G);
-  HIP_TRY(hipMemsetAsync(xs_flags(c), 0, 4, st));
+  // (pass 0: every protocol word, as prepare left them — a retargeted
+  // session starts from the same zeroes)
+  HIP_TRY(hipMemsetAsync(xs_flags(c), 0, pass == 0 ? 32 : 4, st));
   if (pass == 0) {
     if (!counts || !emit || !krange)
       return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null counts / krange");
@@ -3854,10 +4160,10 @@ otsdb_status otsdb_sel_hist_wait(otsdb_ctx* c, void* hip_stream) {
 otsdb_status otsdb_sel_pick_device(otsdb_ctx* c, int64_t* picks,
                                    void* hip_stream) {
   if (!c || !picks) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
+  CtxLock lk(c, /*keep_session=*/true);
   auto& S = c->sel;
   if (!S.active) return fail(OTSDB_E_ILLEGAL_STATE, "no selection session");
-  if (S.next_pass == 0 || S.more)
+  if (S.next_pass == 0 || S.next_pass == -2 || S.more)
     return fail(OTSDB_E_ILLEGAL_STATE, "selection not resolved: run its passes");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
@@ -3886,7 +4192,7 @@ otsdb_status otsdb_sel_pick_device(otsdb_ctx* c, int64_t* picks,
 otsdb_status otsdb_sel_finish_device(otsdb_ctx* c, const int64_t* picks,
                                      otsdb_result* out, void* hip_stream) {
   if (!c || !picks || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
+  CtxLock lk(c, /*keep_session=*/true);
   auto& S = c->sel;
   if (!S.active) return fail(OTSDB_E_ILLEGAL_STATE, "no selection session");
   if (S.next_pass != -1)
@@ -3902,7 +4208,9 @@ otsdb_status otsdb_sel_finish_device(otsdb_ctx* c, const int64_t* picks,
                        S.median, S.P.pct, (const uint32_t*)xs_broken(c));
   otsdb_status rc = compact(c, S.P, G, S.W.out_val, S.W.out_emit, S.W.counts, out);
   if (!rc) rc = finish(c, G, out);
-  S.active = false;
+  // the session stays for otsdb_sel_retarget (the keys are untouched); any
+  // other call of the context ends it
+  S.next_pass = -2;  // finished
   return rc;
 }
 
@@ -4216,7 +4524,7 @@ otsdb_status otsdb_agg_run_cells(otsdb_ctx* c, const otsdb_query_spec* spec,
 
 otsdb_status otsdb_prof_enable(otsdb_ctx* c, int enable) {
   if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
+  CtxLock lk(c, /*keep_session=*/true);
   c->prof = enable != 0;
   return OTSDB_OK;
 }
@@ -4224,7 +4532,7 @@ otsdb_status otsdb_prof_enable(otsdb_ctx* c, int enable) {
 otsdb_status otsdb_prof_read(otsdb_ctx* c, double* ms, int64_t* launches,
                              int n, int reset) {
   if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
+  CtxLock lk(c, /*keep_session=*/true);
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (auto& p : c->ev_pending) {
@@ -4250,19 +4558,19 @@ otsdb_status otsdb_prof_read(otsdb_ctx* c, double* ms, int64_t* launches,
 
 otsdb_status otsdb_ctx_counters(otsdb_ctx* c, int64_t* out, int n) {
   if (!c || (n > 0 && !out)) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
-  const int64_t v[9] = {c->n_cells_uniform, c->n_cells_general,
-                        c->n_cells_uni_miss, c->sel.key_reads, c->sel.passes,
-                        c->n_multi_ds,       c->n_multi_group, c->n_multi_kt,
-                        c->n_multi_tf};
-  for (int i = 0; i < n && i < 9; ++i) out[i] = v[i];
+  CtxLock lk(c, /*keep_session=*/true);
+  const int64_t v[10] = {c->n_cells_uniform, c->n_cells_general,
+                         c->n_cells_uni_miss, c->sel.key_reads, c->sel.passes,
+                         c->n_multi_ds,       c->n_multi_group, c->n_multi_kt,
+                         c->n_multi_tf,       c->sel.sessions};
+  for (int i = 0; i < n && i < 10; ++i) out[i] = v[i];
   return OTSDB_OK;
 }
 
 otsdb_status otsdb_test_set_compact_epoch(otsdb_ctx* c, uint32_t epoch) {
   if (!c || epoch == 0 || epoch >= (1u << 24))
     return fail(OTSDB_E_ILLEGAL_ARGUMENT, "epoch %u", epoch);
-  CtxLock lk(c);
+  CtxLock lk(c, /*keep_session=*/true);
   // forward only: every granule then carries an epoch below the new one
   // until the wrap (a step back would reuse epochs of live granules)
   if (epoch < c->cmp_epoch)

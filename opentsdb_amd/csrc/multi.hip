@@ -7,6 +7,14 @@
 //                       contribution into every requested unordered monoid
 //                       state: the matrix is read once (9 B per series and
 //                       bucket) instead of once per aggregator.
+//                       PARTIAL (otsdb_agg_partials_multi_device): a tile
+//                       that is a whole group packs every state into its
+//                       output's per-(group, bucket) partial instead.
+//   k_partial_empty_multi  the identity state of every output for the groups
+//                       without a member on this rank (PARTIAL only).
+//   k_finalize_ranks_multi  k_finalize_ranks for every output of a
+//                       multi-aggregator call: the ranks' emit bytes read
+//                       once, each output's partials merged in rank order.
 //   k_transform_interp  k_transform's NONE-fill, non-rate branch out of
 //                       place: reads the downsampler's pristine rows, writes
 //                       one interpolation class's matrix.
@@ -31,8 +39,9 @@ OTSDB_MULTI_MONOIDS(OTSDB_X)
 
 struct MultiOut {
   double* val;    // [G * nb]
-  uint8_t* emit;  // [G * nb]
+  uint8_t* emit;  // [G * nb] (PARTIAL: the one emit mask of every output)
   int* err;       // this output's device error word
+  Packed* part;   // [G * nb], PARTIAL only: this output's partials
 };
 
 struct MultiArgs {
@@ -50,6 +59,10 @@ struct MultiArgs {
 // a kernel-uniform mask test — an indexed array of states would live in
 // scratch.  push / finish are the code k_group<M> runs, so each monoid's
 // result is bit-identical to k_group<M> over the same rows and tiles.
+// PARTIAL: the whole-group tile packs each state into the partials of its
+// outputs (what k_combine<M> writes for a group of several tiles) and one
+// emit byte for all of them: emission does not depend on the aggregator.
+template <bool PARTIAL>
 __global__ __launch_bounds__(256) void k_group_multi(
     int64_t nb, int64_t n_tiles, const int64_t* __restrict__ tile_g,
     const int64_t* __restrict__ tile_m0, const int64_t* __restrict__ tile_m1,
@@ -100,7 +113,18 @@ __global__ __launch_bounds__(256) void k_group_multi(
       emit |= sv == ST_REAL;
     }
   }
-  if (tile_single[t]) {
+  if (PARTIAL && tile_single[t]) {
+    const int64_t o = tile_g[t] * nb + b;
+#define OTSDB_X(k, M)                                     \
+  if (mask & (1u << k)) {                                 \
+    const Packed p = s##k.pack();                         \
+    for (int j = 0; j < A.n_out; ++j)                     \
+      if (A.slot[j] == k) A.out[j].part[o] = p;           \
+  }
+    OTSDB_MULTI_MONOIDS(OTSDB_X)
+#undef OTSDB_X
+    A.out[0].emit[o] = (uint8_t)emit;
+  } else if (tile_single[t]) {
     const int64_t o = tile_g[t] * nb + b;
 #define OTSDB_X(k, M)                                     \
   if (mask & (1u << k)) {                                 \
@@ -125,6 +149,82 @@ __global__ __launch_bounds__(256) void k_group_multi(
     OTSDB_MULTI_MONOIDS(OTSDB_X)
 #undef OTSDB_X
     tile_emit[t * nb + b] = (uint8_t)emit;
+  }
+}
+
+// PARTIAL: a group with no member on this rank (no tile: grp_t0 == grp_t1,
+// build_tiles' per-group tile ranges) contributes the identity of every
+// output's monoid (not all-zero bits: min / max start at +-Infinity) and no
+// emission.  One thread per (group, bucket).
+__global__ __launch_bounds__(256) void k_partial_empty_multi(
+    int64_t nb, int64_t n_groups, const int64_t* __restrict__ grp_t0,
+    const int64_t* __restrict__ grp_t1, MultiArgs A) {
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t g = o / nb;
+  if (g >= n_groups || grp_t0[g] != grp_t1[g]) return;
+  for (int j = 0; j < A.n_out; ++j) {
+    const int sl = A.slot[j];
+#define OTSDB_X(k, M) \
+  if (sl == k) A.out[j].part[o] = M::init().pack();
+    OTSDB_MULTI_MONOIDS(OTSDB_X)
+#undef OTSDB_X
+  }
+  A.out[0].emit[o] = 0;
+}
+
+// the slot of dev in FinalizeArgs (its partials come from k_group<MDev>)
+constexpr int kMultiSlotDev = kMultiSlots;
+
+struct FinalizeArgs {
+  int32_t n_out;
+  int32_t slot[OTSDB_MULTI_MAX];  // monoid slot of output i (kMultiSlotDev)
+  MultiOut out[OTSDB_MULTI_MAX];  // dense results and error word of output i
+};
+
+// k_finalize_ranks<M>'s merge of one (group, bucket) of output i:
+// partials [n_ranks][n_out][GB], combined in rank (= series) order
+template <class M>
+DEV double finalize_ranks_one(const Packed* __restrict__ partials, int n_ranks,
+                              int n_out, int i, int64_t GB, int64_t o, int emit,
+                              int* e) {
+  M st = M::init();
+  for (int r = 0; r < n_ranks; ++r)
+    st = M::combine(st, M::unpack(partials[((int64_t)r * n_out + i) * GB + o]));
+  double v = 0.0;
+  if (emit) {
+    v = st.finish(e);
+    if (is_inf(v)) *e |= ERR_INFINITY;
+  }
+  return v;
+}
+
+// multi-GPU, several outputs: one thread per (group, bucket) reads the
+// ranks' emit bytes once, then merges and finishes each output into its own
+// dense result (Infinity / `none` into the output's own error word).  The
+// monoid of an output is a kernel-uniform slot test around one merge each
+// (no indexed array of states, as in k_group_multi); the merge is
+// k_finalize_ranks<M>'s, so output i has the bits of
+// otsdb_agg_finalize_device over slice i.
+__global__ __launch_bounds__(256) void k_finalize_ranks_multi(
+    int64_t GB, int n_ranks, const Packed* __restrict__ partials,
+    const uint8_t* __restrict__ emits, FinalizeArgs A) {
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= GB) return;
+  int emit = 0;
+  for (int r = 0; r < n_ranks; ++r) emit |= emits[(int64_t)r * GB + o];
+  for (int i = 0; i < A.n_out; ++i) {
+    const int sl = A.slot[i];
+    double v = 0.0;
+    int e = 0;
+#define OTSDB_X(k, M) \
+  if (sl == k)        \
+    v = finalize_ranks_one<M>(partials, n_ranks, A.n_out, i, GB, o, emit, &e);
+    OTSDB_MULTI_MONOIDS(OTSDB_X)
+    OTSDB_X(kMultiSlotDev, MDev)
+#undef OTSDB_X
+    if (e) atomicOr(A.out[i].err, e);
+    A.out[i].val[o] = v;
+    A.out[i].emit[o] = (uint8_t)emit;
   }
 }
 

@@ -20,6 +20,11 @@ and the last rank's states are broadcast (hand_on_partials).  Raw
 (non-downsampled) queries, whose union-timestamp merge needs every member's
 points, run the groups spanning ranks as replicas over all-gathered member
 series (gather_shared_series).
+Several aggregators of one query (run_sharded_multi): the scalar ones share
+one downsample pass per rank, one all-gather of their partials and one
+finalize (otsdb_agg_partials_multi_device / _finalize_multi_device);
+several medians / percentiles share one selection session
+(otsdb_sel_retarget, run_sharded_select_multi).
 """
 import numpy as np
 
@@ -284,6 +289,22 @@ def _agg_name(spec):
     return core.Aggregators.by_id(spec.agg_id).registry_name
 
 
+def _shard_plan(engine, spec, dbatch, n_groups_global, group=None):
+    """The ShardPlan of (engine, spec, batch), cached on the batch itself (an
+    id()-keyed cache can hand a freed batch's plan to a new one on one rank
+    only, which then skips the classification all-reduce the other ranks
+    wait in)."""
+    plans = getattr(dbatch, "_shard_plans", None)
+    if plans is None:
+        plans = dbatch._shard_plans = {}
+    key = (id(engine), bytes(memoryview(spec).cast("B")), n_groups_global)
+    plan = plans.get(key)
+    if plan is None:
+        plan = plans[key] = ShardPlan(engine, spec, dbatch, n_groups_global,
+                                      group)
+    return plan
+
+
 def run_sharded(engine, spec, dbatch, n_groups_global, torch_mod=None,
                 group=None, plan=None):
     """Runs one query over a rank's DeviceBatch whose group_offsets span all
@@ -297,17 +318,7 @@ def run_sharded(engine, spec, dbatch, n_groups_global, torch_mod=None,
     from .engine import DeviceResult, run_device
 
     if plan is None:
-        # cached on the batch itself (an id()-keyed cache can hand a freed
-        # batch's plan to a new one on one rank only, which then skips the
-        # classification all-reduce the other ranks wait in)
-        plans = getattr(dbatch, "_shard_plans", None)
-        if plans is None:
-            plans = dbatch._shard_plans = {}
-        key = (id(engine), bytes(memoryview(spec).cast("B")), n_groups_global)
-        plan = plans.get(key)
-        if plan is None:
-            plan = plans[key] = ShardPlan(engine, spec, dbatch,
-                                          n_groups_global, group)
+        plan = _shard_plan(engine, spec, dbatch, n_groups_global, group)
     if len(plan.local):
         run_device(engine, spec, plan.local_batch, plan.local_res)
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -421,6 +432,17 @@ class ShardedSelect:
             self.engine.ctx, self.picks.data_ptr(), self._stream()))
         return self.picks
 
+    def retarget(self, agg):
+        """otsdb_sel_retarget: re-aims the prepared session at another
+        median / p* / ep* (`agg`: an Aggregators entry, a name or an id).
+        The caller runs hist_pass(0) .. pick .. finish again over the same
+        all-reduced counts / emit / krange; nothing is prepared again."""
+        from .engine import multi_args
+        _, ids, _ = multi_args([agg])
+        self.engine._check(self.engine.lib.otsdb_sel_retarget(
+            self.engine.ctx, int(ids[0])))
+        self.spec = _spec_with(self.spec, int(ids[0]), self.spec.interp)
+
     def finish(self):
         import ctypes as C
         import torch
@@ -443,10 +465,20 @@ def run_sharded_select(engine, spec, dbatch, n_groups_global, group=None):
     all-reduces of the counts, key ranges, each pass's histograms and the
     picked keys."""
     sel = ShardedSelect(engine, spec, dbatch, n_groups_global)
+    _sel_prepare(sel, group)
+    return _sel_resolve(sel, group)
+
+
+def _sel_prepare(sel, group=None):
     counts, emit, krange = sel.prepare()
     all_reduce(counts, "sum", group)
     all_reduce(emit, "max", group)
     all_reduce(krange, "min", group)
+
+
+def _sel_resolve(sel, group=None):
+    """The pass loop, the pick and the finish of the session's current
+    aggregator."""
     p = 0
     while sel.hist_pass(p):
         if p >= MAX_SEL_PASSES:
@@ -460,6 +492,131 @@ def run_sharded_select(engine, spec, dbatch, n_groups_global, group=None):
         sel.wait()
     all_reduce(picks, "sum", group)
     return sel.finish()
+
+
+def _is_selection(agg_id):
+    return agg_id == 5 or agg_id >= 17  # median, p*, ep*
+
+
+def _spec_with(spec, agg_id, interp):
+    """A copy of `spec` with its cross-series aggregator / interpolation
+    replaced (what a multi-aggregator call evaluates for one output)."""
+    s = type(spec).from_buffer_copy(spec)
+    s.agg_id = int(agg_id)
+    s.interp = int(interp)
+    return s
+
+
+def run_sharded_select_multi(engine, spec, aggs, dbatch, n_groups_global,
+                             group=None):
+    """Several medians / percentiles of one query over series-sharded
+    groups from ONE selection session: one prepare (downsample, key
+    transpose) and one all-reduce each of the counts, emit flags and key
+    ranges; then per aggregator the pass loop, the pick and the finish
+    (otsdb_sel_retarget between them).  Returns one DeviceResult per
+    aggregator, the bits of run_sharded_select for each."""
+    from .core import IllegalArgumentException
+    from .engine import multi_args
+    _, ids, _ = multi_args(aggs)
+    for a in ids:
+        if not _is_selection(int(a)):
+            raise IllegalArgumentException(
+                "aggregator %d is no median / percentile" % int(a))
+    sel = ShardedSelect(engine, _spec_with(spec, ids[0], spec.interp), dbatch,
+                        n_groups_global)
+    _sel_prepare(sel, group)
+    outs = []
+    for i, a in enumerate(ids):
+        if i:
+            sel.retarget(int(a))
+        outs.append(_sel_resolve(sel, group))
+    return outs
+
+
+def run_sharded_multi(engine, spec, aggs, dbatch, n_groups_global,
+                      interps=None, group=None):
+    """Several cross-series aggregators of one query over series-sharded
+    ranks (`spec` with its aggregator replaced by each of `aggs`, as
+    Engine.run_multi).  Returns one result per aggregator, in order, each
+    with the n_points() / host_groups() of the matching single call.
+
+    Downsampled queries, scalar aggregators: the groups this rank holds
+    alone finish in one run_multi_device; the groups spanning ranks take one
+    otsdb_agg_partials_multi_device (one downsample pass), ONE all-gather of
+    the [n_out][GB] partials and one of the emit bytes, then
+    otsdb_agg_finalize_multi_device.  A `dev` whose shared groups are handed
+    on as chains keeps run_sharded for that output alone.  Medians /
+    percentiles: run_sharded_select_multi (one session).  A mixed set runs
+    both paths: two downsample passes, not n_out.  Raw (non-downsampled)
+    queries run run_sharded_raw once per output."""
+    import torch
+    from .engine import (DeviceResult, finalize_multi_device, multi_args,
+                         partials_multi_device, run_multi_device)
+    n, ids, it = multi_args(aggs, interps)
+    specs = [_spec_with(spec, ids[i], it[i]) for i in range(n)]
+    if not (spec.ds_interval_ms > 0 or spec.run_all):
+        return [run_sharded_raw(engine, s, dbatch, n_groups_global, group)
+                for s in specs]
+    results = [None] * n
+    # ---- selections: one session per interpolation asked for
+    by_interp = {}
+    for i in range(n):
+        if _is_selection(int(ids[i])):
+            by_interp.setdefault(int(it[i]), []).append(i)
+    for interp, idx in by_interp.items():
+        res = run_sharded_select_multi(
+            engine, _spec_with(spec, ids[idx[0]], interp),
+            [int(ids[i]) for i in idx], dbatch, n_groups_global, group)
+        for i, r in zip(idx, res):
+            results[i] = _SelResult(r)
+    # ---- order-sensitive outputs whose shared groups are handed on
+    todo = []
+    for i in range(n):
+        if results[i] is not None:
+            continue
+        if _agg_name(specs[i]) in ORDERED_AGGS:
+            plan = _shard_plan(engine, specs[i], dbatch, n_groups_global,
+                               group)
+            if len(plan.chain):
+                results[i] = run_sharded(engine, specs[i], dbatch,
+                                         n_groups_global, group=group,
+                                         plan=plan)
+                continue
+        todo.append(i)
+    if not todo:
+        return results
+    # ---- the scalar set: shared rows, partials and collectives
+    plan = _shard_plan(engine, specs[todo[0]], dbatch, n_groups_global, group)
+    m = len(todo)
+    m_ids, m_it = [int(ids[i]) for i in todo], [int(it[i]) for i in todo]
+    dev = dbatch.ts.device
+    local = plan.__dict__.setdefault("_multi_local", {}).get(m)
+    if local is None:
+        local = plan._multi_local[m] = [
+            DeviceResult(torch, len(plan.local), plan.local_res.cap, dev)
+            for _ in range(m)]
+    if len(plan.local):
+        run_multi_device(engine, spec, m_ids, plan.local_batch, local,
+                         interps=m_it)
+    merged = [None] * m
+    if len(plan.merge):
+        stream = torch.cuda.current_stream().cuda_stream
+        nb, GB = plan.nb, len(plan.merge) * plan.nb
+        parts = torch.zeros((m, max(GB, 1), PARTIAL_WORDS), dtype=torch.int64,
+                            device=dev)
+        emit = torch.zeros(max(GB, 1), dtype=torch.uint8, device=dev)
+        partials_multi_device(engine, spec, m_ids, plan.shared_batch, parts,
+                              emit, stream=stream, interps=m_it)
+        gp, ge = all_gather_partials(
+            parts[:, :GB].reshape(m * GB, PARTIAL_WORDS), emit[:GB], group)
+        merged = [DeviceResult(torch, len(plan.merge), max(GB, 1), dev)
+                  for _ in range(m)]
+        finalize_multi_device(engine, spec, m_ids, len(plan.merge), nb,
+                              plan.world, gp.contiguous(), ge.contiguous(),
+                              merged, stream=stream, interps=m_it)
+    for j, i in enumerate(todo):
+        results[i] = ShardedResult(plan.local, local[j], plan.merge, merged[j])
+    return results
 
 
 def shard_host_batch(hb, world, rank, by_points=True):

@@ -159,6 +159,13 @@ class Engine:
         return dict(downsample_passes=out[5], group_passes=out[6],
                     key_transposes=out[7], transform_passes=out[8])
 
+    def sel_sessions(self):
+        """otsdb_ctx_counters [9]: otsdb_sel_* sessions prepared since the
+        context was created (a retargeted session counts once)."""
+        out = (C.c_int64 * 10)()
+        self._check(self.lib.otsdb_ctx_counters(self.ctx, out, 10))
+        return int(out[9])
+
     def close(self):
         if self.ctx:
             self.lib.otsdb_ctx_destroy(self.ctx)
@@ -362,3 +369,36 @@ def run_multi_device(engine, spec, aggs, dbatch, dresults, stream=None,
     engine._check(engine.lib.otsdb_agg_run_multi_device(
         engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
         C.byref(b), rs, None if stream is None else C.c_void_p(stream)))
+
+
+def partials_multi_device(engine, spec, aggs, dbatch, partials, emit,
+                          stream=None, interps=None):
+    """otsdb_agg_partials_multi_device: one downsample pass of this rank's
+    shard, output i's per-(group, bucket) states into partials[i] (an int64
+    tensor [n_out, G * n_buckets, 4] of raw otsdb_partial words), one emit
+    mask [G * n_buckets] (uint8) for all outputs."""
+    n, ids, it = multi_args(aggs, interps)
+    b = _abi_cached(dbatch, _BATCH_TENSORS, dbatch.as_abi,
+                    dbatch.group_offsets._version)
+    engine._check(engine.lib.otsdb_agg_partials_multi_device(
+        engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
+        C.byref(b), partials.data_ptr(), emit.data_ptr(),
+        None if stream is None else C.c_void_p(stream)))
+
+
+def finalize_multi_device(engine, spec, aggs, n_groups, n_buckets, n_ranks,
+                          partials, emit, dresults, stream=None, interps=None):
+    """otsdb_agg_finalize_multi_device: partials [n_ranks, n_out, G *
+    n_buckets, 4] and emit [n_ranks, G * n_buckets] merged in rank order,
+    output i into dresults[i]."""
+    n, ids, it = multi_args(aggs, interps)
+    if len(dresults) != n:
+        raise IllegalArgumentException(
+            "%d results for %d aggregators" % (len(dresults), n))
+    rs = (abi.Result * n)()
+    for i, r in enumerate(dresults):
+        rs[i] = r.as_abi()
+    engine._check(engine.lib.otsdb_agg_finalize_multi_device(
+        engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
+        int(n_groups), int(n_buckets), int(n_ranks), partials.data_ptr(),
+        emit.data_ptr(), rs, None if stream is None else C.c_void_p(stream)))
