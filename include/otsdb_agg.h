@@ -320,6 +320,55 @@ otsdb_status otsdb_agg_run_multi(otsdb_ctx* ctx, const otsdb_query_spec* spec,
                                  const int32_t* interps,
                                  const otsdb_batch* batch, otsdb_result* outs);
 
+/* ---- several downsampling functions over one point-stream pass ---------- */
+/* The sub-queries of one panel that share spans, window, interval, fill
+ * policy and groups and differ in the DOWNSAMPLING function as well as in
+ * the aggregator — the envelope panel min:5m-min / avg:5m-avg / max:5m-max
+ * (one TSQuery carries several TSSubQuerys over the same data,
+ * TSQuery.java:172-214; each becomes its own TsdbQuery run,
+ * TsdbQuery.java:992-1113).  Output i is the single query with
+ * ds_agg_ids[i] / agg_ids[i] / interps[i] in place of spec->ds_agg_id /
+ * spec->agg_id / spec->interp, which are ignored; duplicates are allowed.
+ * Functions of the envelope set — sum (zimsum, pfsum), avg, count, min
+ * (mimmin), max (mimmax) — are reduced from ONE pass over the point stream
+ * into one row matrix per distinct function, bit for bit the rows of the
+ * single function's pass; each matrix then goes through the multi-aggregator
+ * group stage for the outputs that use it.  Everything else
+ * runs function by function, one multi-aggregator call per distinct
+ * function: a function outside the set, rate, per-series calendar anchors,
+ * raw group-by (no downsampler: ds_agg_ids is ignored), grids past the row
+ * limits, a single distinct function.  Same results either way.
+ * n_out outside [1, OTSDB_MULTI_MAX] or a null id array:
+ * OTSDB_E_ILLEGAL_ARGUMENT; an unknown aggregator or downsampler id:
+ * OTSDB_E_NO_SUCH_ELEMENT; `none` as a downsampler:
+ * OTSDB_E_ILLEGAL_ARGUMENT.  When several outputs fail the call returns the
+ * status of the lowest-index one; the outputs before it are complete.
+ * otsdb_ctx_counters [10] / [11]: passes over the point stream / row
+ * matrices built by the last panel call.
+ * plan_panel: max_out_points bounds EACH output, workspace_bytes the call.  */
+otsdb_status otsdb_agg_plan_panel(otsdb_ctx* ctx, const otsdb_query_spec* spec,
+                                  int32_t n_out, const int32_t* ds_agg_ids,
+                                  const int32_t* agg_ids,
+                                  const int32_t* interps,
+                                  const otsdb_batch* batch, otsdb_sizes* out);
+/* outs: n_out results (HOST array of structs; DEVICE pointers inside).
+ * TSQuery.java:172-214 / TsdbQuery.java:992-1113.                           */
+otsdb_status otsdb_agg_run_panel_device(otsdb_ctx* ctx,
+                                        const otsdb_query_spec* spec,
+                                        int32_t n_out,
+                                        const int32_t* ds_agg_ids,
+                                        const int32_t* agg_ids,
+                                        const int32_t* interps,
+                                        const otsdb_batch* batch,
+                                        otsdb_result* outs, void* hip_stream);
+/* Host pointers throughout (TSQuery.java:172-214 / TsdbQuery.java:992-1113);
+ * otsdb_agg_run's OTSDB_E_CAPACITY contract holds per result (the offsets of
+ * a result too small are still whole).                                      */
+otsdb_status otsdb_agg_run_panel(otsdb_ctx* ctx, const otsdb_query_spec* spec,
+                                 int32_t n_out, const int32_t* ds_agg_ids,
+                                 const int32_t* agg_ids, const int32_t* interps,
+                                 const otsdb_batch* batch, otsdb_result* outs);
+
 /* ---- multi-GPU (series-sharded) ----------------------------------------- */
 /* Partial per-(group, bucket) reduction state, the unit exchanged between
  * ranks over RCCL.  32 bytes, see DESIGN.md §Multi-GPU.                     */
@@ -672,7 +721,9 @@ otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
  * (bucketize) passes over the point stream, out[6] group-stage passes over
  * a row matrix, out[7] key transposes, out[8] transform passes (one per
  * interpolation class).  out[9]: otsdb_sel_* sessions prepared since the
- * context was created (otsdb_sel_retarget prepares none).                  */
+ * context was created (otsdb_sel_retarget prepares none).  Of the last
+ * otsdb_agg_run_panel* call: out[10] passes over the point stream, out[11]
+ * row matrices built (the multi calls inside it still maintain [5..8]).    */
 otsdb_status otsdb_ctx_counters(otsdb_ctx* ctx, int64_t* out, int n);
 /* Test hook: the one-pass compaction's epoch (1 .. 2^24 - 1, forward only)
  * the context's next call increments, so tests can drive it to its wrap.  */

@@ -154,6 +154,8 @@ EXPORTS = [
     "otsdb_agg_run_multi", "otsdb_agg_run_cells_multi_device",
     "otsdb_agg_partials_multi_device", "otsdb_agg_finalize_multi_device",
     "otsdb_sel_retarget",
+    "otsdb_agg_plan_panel", "otsdb_agg_run_panel_device",
+    "otsdb_agg_run_panel",
 ]
 
 MULTI_MAX = 32  # OTSDB_MULTI_MAX
@@ -267,6 +269,18 @@ def load(path=None):
     lib.otsdb_agg_finalize_multi_device.argtypes = [vp, PS, i32, vp, vp, i64,
                                                     i64, i32, vp, vp, PR, vp]
     lib.otsdb_agg_finalize_multi_device.restype = C.c_int
+    # several downsampling functions over one point-stream pass: the multi
+    # entries' arguments with ds_agg_ids before agg_ids (absent from builds
+    # of earlier commits, which abi.load still takes for A/B runs)
+    if hasattr(lib, "otsdb_agg_run_panel"):
+        lib.otsdb_agg_plan_panel.argtypes = [vp, PS, i32, vp, vp, vp, PB,
+                                             C.POINTER(Sizes)]
+        lib.otsdb_agg_plan_panel.restype = C.c_int
+        lib.otsdb_agg_run_panel_device.argtypes = [vp, PS, i32, vp, vp, vp, PB,
+                                                   PR, vp]
+        lib.otsdb_agg_run_panel_device.restype = C.c_int
+        lib.otsdb_agg_run_panel.argtypes = [vp, PS, i32, vp, vp, vp, PB, PR]
+        lib.otsdb_agg_run_panel.restype = C.c_int
     # bound only on the ABI it was added to: a stale library of another
     # version must not hand out a symbol of other arguments
     if lib.otsdb_abi_version() == 6 and hasattr(lib, "otsdb_sel_retarget"):

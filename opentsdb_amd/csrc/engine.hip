@@ -31,6 +31,7 @@
 #include "rows.hip"
 #include "calendar.hip"
 #include "multi.hip"
+#include "panel.hip"
 #include "launch.h"
 
 using namespace otsdb;
@@ -292,6 +293,9 @@ struct otsdb_ctx {
   // the point stream, group-stage passes over a row matrix, key transposes,
   // transform passes
   int64_t n_multi_ds = 0, n_multi_group = 0, n_multi_kt = 0, n_multi_tf = 0;
+  // otsdb_ctx_counters [10..11], of the last panel call: passes over the
+  // point stream, row matrices built
+  int64_t n_panel_passes = 0, n_panel_mats = 0;
   // cross-rank selection session (otsdb_sel_*): lives in `ws` between calls
   struct {
     bool active = false;
@@ -1954,6 +1958,9 @@ struct MultiReq {
   const int32_t* aggs;
   const int32_t* interps;  // null: every output its aggregator's own
   otsdb_result* outs;
+  // the request's first error word / compaction slot (d_merr, h_mdone): the
+  // functions of a panel call run as one request each over one set of slots
+  int32_t e0 = 0;
 };
 
 otsdb_query_spec multi_spec(const otsdb_query_spec* s, const MultiReq& q,
@@ -2010,16 +2017,20 @@ int multi_classes(const MultiReq& q, const Params& P, int* cls, int* interp) {
 // would first trim to the data (past 4e9 cells), dev past the row budget
 // (with the pristine rows kept beside a class matrix: twice the rows).  Such
 // calls run their outputs one after another through the single-query path.
+// A panel call asks per downsampling function (panel_shared): a function may
+// have one output (min_n = 1), and the cell and row budgets hold for the
+// `mats` row matrices of the call together.
 bool multi_shares_rows(const otsdb_query_spec* spec, const MultiReq& q,
                        const Params& P, int64_t S,
-                       const std::vector<int64_t>& goff) {
-  if (q.n < 2) return false;
+                       const std::vector<int64_t>& goff, int min_n = 2,
+                       int mats = 1) {
+  if (q.n < min_n) return false;
   if (!(spec->ds_interval_ms > 0 || spec->run_all) || anchored(spec))
     return false;
   const int64_t G = (int64_t)goff.size() - 1;
   if (S <= 0 || G <= 0 || P.nb <= 0 || goff.back() <= 0) return false;
   if (P.nb > (int64_t)INT32_MAX - 2) return false;
-  const double rows = (double)S * (double)P.nb;
+  const double rows = (double)S * (double)P.nb * (double)mats;
   if (rows > 4.0e9) return false;
   int cls[OTSDB_MULTI_MAX], ci[OTSDB_MULTI_MAX];
   const int n_cls = multi_classes(q, P, cls, ci);
@@ -2060,6 +2071,16 @@ struct MultiState {
   int64_t chunk, whole;
 };
 
+// multi_build as one downsampling function of a panel call (panel_shared):
+// the function's buffers are carved at ws_off of a workspace the panel call
+// sizes (size_only: the sizing pass) and clears; the call builds the rows of
+// all its functions itself, in one pass.
+struct PanelPart {
+  size_t ws_off;
+  size_t ws_need;  // out: bytes of this function's carve
+  bool size_only;
+};
+
 otsdb_status multi_buffers(otsdb_ctx* c) {
   if (c->d_merr) return OTSDB_OK;
   HIP_TRY(hipMalloc(&c->d_merr, OTSDB_MULTI_MAX * sizeof(int)));
@@ -2080,7 +2101,7 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
                          const int64_t* d_members, std::vector<int64_t>& goff,
                          const Params& P0, const CellsDev* cells,
                          const int64_t* series_row, MultiState& M,
-                         bool partial = false) {
+                         bool partial = false, PanelPart* part = nullptr) {
   hipStream_t st = c->stream;
   otsdb_status rc = multi_buffers(c);
   if (rc) return rc;
@@ -2191,21 +2212,28 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
     }
     return cv.off + 256;
   };
-  rc = ensure(&c->ws, &c->ws_cap, carve(nullptr));
-  if (rc) return rc;
-  carve((char*)c->ws);
+  if (part) {
+    part->ws_need = carve(nullptr);
+    if (part->size_only) return OTSDB_OK;
+    carve((char*)c->ws + part->ws_off);
+  } else {
+    rc = ensure(&c->ws, &c->ws_cap, carve(nullptr));
+    if (rc) return rc;
+    carve((char*)c->ws);
 
-  // every output its own error word; the shared stages report into the
-  // context's (folded into every output's status at the end)
-  HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(int), st));
-  HIP_TRY(hipMemsetAsync(c->d_merr, 0, OTSDB_MULTI_MAX * sizeof(int), st));
-  c->clean_entry = false;
+    // every output its own error word; the shared stages report into the
+    // context's (folded into every output's status at the end)
+    HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(c->d_merr, 0, OTSDB_MULTI_MAX * sizeof(int), st));
+    c->clean_entry = false;
+  }
   if (M.empty_group && !partial) {
     HIP_TRY(hipMemsetAsync(W.out_emit, 0, (size_t)G * NB, st));
     for (int i = 0; i < q.n; ++i)
       HIP_TRY(hipMemsetAsync(M.out_emit[i], 0, (size_t)G * NB, st));
   }
   if (!P.sentinel) HIP_TRY(hipMemsetAsync(W.R.state, 0, rows, st));
+  if (part) return OTSDB_OK;  // (the panel call's one pass builds the rows)
   c->n_multi_ds = c->n_multi_group = c->n_multi_kt = c->n_multi_tf = 0;
   rc = build_rows(c, spec, P, B, W, cells, series_row, M.rate_fused);
   if (rc) return rc;
@@ -2256,19 +2284,27 @@ void multi_scalar_args(const MultiState& M, int k, MultiArgs& MA, int* who) {
 
 // Every output through the existing compaction into its own result, one
 // synchronisation, the status of the lowest-index failing output.
-otsdb_status multi_compact_outputs(otsdb_ctx* c, const MultiReq& q,
-                                   const Params& P, int64_t G,
-                                   double* const* out_val,
-                                   uint8_t* const* out_emit) {
-  hipStream_t st = c->stream;
-  otsdb_status rc;
+otsdb_status multi_compact_launch(otsdb_ctx* c, const MultiReq& q,
+                                  const Params& P, int64_t G,
+                                  double* const* out_val,
+                                  uint8_t* const* out_emit) {
   for (int i = 0; i < q.n; ++i) {
     Params Pi = P;
     agg_params(&Pi, q.aggs[i], q.interps ? q.interps[i] : OTSDB_INTERP_DEFAULT);
-    rc = compact(c, Pi, G, out_val[i], out_emit[i], nullptr, &q.outs[i],
-                 c->d_merr + i, c->d_mdone + 4 * i);
+    const otsdb_status rc =
+        compact(c, Pi, G, out_val[i], out_emit[i], nullptr, &q.outs[i],
+                c->d_merr + q.e0 + i, c->d_mdone + 4 * (q.e0 + i));
     if (rc) return rc;
   }
+  return OTSDB_OK;
+}
+
+// The one synchronisation and the statuses of the compacted outputs.  orig:
+// the caller's index of each output (a panel call runs them grouped by
+// function); the lowest of those decides.
+otsdb_status multi_compact_wait(otsdb_ctx* c, const MultiReq& q,
+                                const int* orig = nullptr) {
+  hipStream_t st = c->stream;
   // (the next call of any kind clears the context's word itself: err_clean
   // stays false, as after a single query that did not end in k_compact1)
   c->small_ready = false;
@@ -2277,30 +2313,51 @@ otsdb_status multi_compact_outputs(otsdb_ctx* c, const MultiReq& q,
                          hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const int shared = (int)(c->h_small[0] & 0xFFFFFFFF);
-  for (int i = 0; i < q.n; ++i) {
-    int64_t* d = c->h_mdone + 4 * i;
+  int failed = -1;
+  otsdb_status failed_rc = OTSDB_OK;
+  std::string failed_msg;
+  for (int j = 0; j < q.n; ++j) {
+    const int i = orig ? orig[j] : j;
+    int64_t* d = c->h_mdone + 4 * (q.e0 + j);
     int e = shared | (int)(__atomic_load_n(&d[0], __ATOMIC_ACQUIRE) & 0xFFFFFFFF);
     c->multi_total[i] = __atomic_load_n(&d[1], __ATOMIC_ACQUIRE);
     if (__atomic_load_n(&d[2], __ATOMIC_ACQUIRE)) {
       d[2] = 0;
       e |= ERR_INTERNAL;
     }
-    rc = result_status(e, c->multi_total[i], q.outs[i].capacity);
-    if (rc) {
-      c->multi_failed = i;
-      if (rc == OTSDB_E_CAPACITY) c->result_short = true;
-      return rc;
+    const otsdb_status rc =
+        result_status(e, c->multi_total[i], q.outs[j].capacity);
+    if (rc && (failed < 0 || i < failed)) {
+      failed = i;
+      failed_rc = rc;
+      failed_msg = g_last_error;
     }
+    if (rc && !orig) break;
   }
-  return OTSDB_OK;
+  if (failed < 0) return OTSDB_OK;
+  c->multi_failed = failed;
+  if (failed_rc == OTSDB_E_CAPACITY) c->result_short = true;
+  g_last_error = failed_msg;
+  return failed_rc;
+}
+
+otsdb_status multi_compact_outputs(otsdb_ctx* c, const MultiReq& q,
+                                   const Params& P, int64_t G,
+                                   double* const* out_val,
+                                   uint8_t* const* out_emit) {
+  const otsdb_status rc = multi_compact_launch(c, q, P, G, out_val, out_emit);
+  if (rc) return rc;
+  return multi_compact_wait(c, q);
 }
 
 // "Aggregate the rows" per interpolation class and output, compact every
 // output into its result, synchronise once and report the status of the
 // lowest-index failing output.
-otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M) {
+otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M,
+                             bool compact_now = true) {
   hipStream_t st = c->stream;
   const MultiReq& q = M.q;
+  int* const merr = c->d_merr + q.e0;  // this request's error words
   const int64_t G = M.G, NB = M.NB, S = M.S;
   Params& P = M.P;
   otsdb_status rc;
@@ -2326,7 +2383,7 @@ otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M) {
       double pct;
       sel_of(i, &median, &pct);
       sel_fused_select(c, M.W, T, NB, A, median, pct, M.out_val[i],
-                       M.out_emit[i], c->d_merr + i);
+                       M.out_emit[i], merr + i);
       ++c->n_multi_group;
     }
   }
@@ -2345,7 +2402,7 @@ otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M) {
     multi_scalar_args(M, k, MA, who);
     for (int j = 0; j < MA.n_out; ++j)
       MA.out[j] = MultiOut{M.out_val[who[j]], M.out_emit[who[j]],
-                           c->d_merr + who[j], nullptr};
+                           merr + who[j], nullptr};
     if (MA.n_out > 0 && T.T > 0) {
       hipLaunchKernelGGL(k_group_multi<false>, dim3(blocks_for(T.T * NB, 256)),
                          dim3(256), 0, st, NB, T.T, T.tg, T.tm0, T.tm1,
@@ -2359,7 +2416,7 @@ otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M) {
           with_monoid(q.aggs[i], [&](auto tag) {
             launch_combine<decltype(tag)>(c, Ws, NB, T.MG, T.mg, T.mt0, T.mt1,
                                           M.out_val[i], M.out_emit[i], nullptr,
-                                          M.two_level, 0, c->d_merr + i);
+                                          M.two_level, 0, merr + i);
           });
         }
     }
@@ -2388,7 +2445,7 @@ otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M) {
       double pct;
       sel_of(i, &median, &pct);
       sel_finish(c, Wo, T, NB, A, median, pct, /*transpose=*/false,
-                 c->d_merr + i);
+                 merr + i);
       ++c->n_multi_group;
     }
     // ---- the ordered outputs (dev): their own group pass over the tiles
@@ -2408,12 +2465,14 @@ otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M) {
       Work Wd = Wc;
       Wd.out_val = M.out_val[i];
       Wd.out_emit = M.out_emit[i];
-      rc = group_rows(c, q.aggs[i], Wd, Td, NB, G, Ad, c->d_merr + i);
+      rc = group_rows(c, q.aggs[i], Wd, Td, NB, G, Ad, merr + i);
       if (rc) return rc;
       ++c->n_multi_group;
     }
   }
   HIP_TRY(hipGetLastError());
+  // (a panel call compacts the outputs of all its functions, then waits once)
+  if (!compact_now) return OTSDB_OK;
   return multi_compact_outputs(c, q, P, G, M.out_val, M.out_emit);
 }
 
@@ -2530,6 +2589,278 @@ otsdb_status run_multi_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   rc = multi_build(c, &s0, q, B, b->group_members, goff, P, nullptr, nullptr, M);
   if (rc) return rc;
   return multi_aggregate(c, M);
+}
+
+// ------------------------------------------------------------ panel queries
+// otsdb_agg_run_panel*: n outputs that differ in the downsampling function
+// as well as in the cross-series aggregator.  DESIGN.md §4.2.
+struct PanelReq {
+  int32_t n;
+  const int32_t* ds;
+  const int32_t* aggs;
+  const int32_t* interps;  // null: every output its aggregator's own
+  otsdb_result* outs;
+};
+
+otsdb_query_spec panel_spec(const otsdb_query_spec* s, const PanelReq& q,
+                            int i) {
+  otsdb_query_spec r = *s;
+  r.ds_agg_id = q.ds[i];
+  r.agg_id = q.aggs[i];
+  r.interp = q.interps ? q.interps[i] : OTSDB_INTERP_DEFAULT;
+  return r;
+}
+
+otsdb_status check_panel(const otsdb_query_spec* spec, const PanelReq& q) {
+  if (q.n < 1 || q.n > OTSDB_MULTI_MAX)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "n_out %d outside [1, %d]", (int)q.n,
+                OTSDB_MULTI_MAX);
+  if (!q.ds || !q.aggs)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null ds_agg_ids / agg_ids");
+  const bool ds = spec->ds_interval_ms > 0 || spec->run_all;
+  for (int i = 0; i < q.n; ++i) {
+    // (raw group-by has no downsampler: the functions are ignored)
+    if (ds && (q.ds[i] < 0 || q.ds[i] >= OTSDB_AGG_COUNT_IDS))
+      return fail(OTSDB_E_NO_SUCH_ELEMENT, "No such downsampling function: %d",
+                  q.ds[i]);
+    const otsdb_query_spec si = panel_spec(spec, q, i);
+    const otsdb_status rc = check_spec(&si);
+    if (rc) return rc;
+  }
+  return OTSDB_OK;
+}
+
+// the envelope row of a downsampling function (panel.hip), 0: not in the set
+uint32_t panel_fn(int ds) {
+  switch (ds) {
+    case OTSDB_AGG_SUM:
+    case OTSDB_AGG_PFSUM:
+    case OTSDB_AGG_ZIMSUM: return PF_SUM;
+    case OTSDB_AGG_AVG: return PF_AVG;
+    case OTSDB_AGG_COUNT: return PF_CNT;
+    case OTSDB_AGG_MIN:
+    case OTSDB_AGG_MIMMIN: return PF_MIN;
+    case OTSDB_AGG_MAX:
+    case OTSDB_AGG_MIMMAX: return PF_MAX;
+    default: return 0;
+  }
+}
+
+// One distinct downsampling function of a panel request and its outputs (in
+// the caller's order).  Aliases of one reduction (sum / zimsum / pfsum, min /
+// mimmin, max / mimmax) are one function.
+struct PanelFunc {
+  int ds;        // the id its calls run with
+  uint32_t fn;   // envelope row, or 0
+  std::vector<int> idx;
+  std::vector<int32_t> aggs, interps;
+  std::vector<otsdb_result> outs;
+  MultiReq req(const PanelReq& q, int e0) {
+    MultiReq r{(int32_t)idx.size(), aggs.data(),
+               q.interps ? interps.data() : nullptr, outs.data()};
+    r.e0 = e0;
+    return r;
+  }
+};
+
+std::vector<PanelFunc> panel_funcs(const otsdb_query_spec* spec,
+                                   const PanelReq& q) {
+  const bool ds = spec->ds_interval_ms > 0 || spec->run_all;
+  std::vector<PanelFunc> F;
+  for (int i = 0; i < q.n; ++i) {
+    const int id = ds ? q.ds[i] : spec->ds_agg_id;
+    const uint32_t fn = ds ? panel_fn(id) : 0;
+    size_t k = 0;
+    while (k < F.size() && !(fn ? F[k].fn == fn : (!F[k].fn && F[k].ds == id)))
+      ++k;
+    if (k == F.size()) {
+      F.emplace_back();
+      F[k].ds = id;
+      F[k].fn = fn;
+    }
+    F[k].idx.push_back(i);
+    F[k].aggs.push_back(q.aggs[i]);
+    F[k].interps.push_back(q.interps ? q.interps[i] : OTSDB_INTERP_DEFAULT);
+    F[k].outs.push_back(q.outs[i]);
+  }
+  return F;
+}
+
+// what a panel call remembers of its sub-calls: the totals in the caller's
+// order and the failing output of the lowest index
+struct PanelOutcome {
+  int64_t total[OTSDB_MULTI_MAX] = {0};
+  int failed = -1;
+  otsdb_status rc = OTSDB_OK;
+  std::string msg;
+  bool result_short = false;
+  void fail_at(otsdb_ctx* c, int i, otsdb_status r) {
+    if (failed >= 0 && failed <= i) return;
+    failed = i;
+    rc = r;
+    msg = g_last_error;
+    result_short = c->result_short;
+  }
+};
+
+// The envelope functions E of a request over one pass of the point stream:
+// every function's buffers carved from one workspace (multi_build), prep, the
+// envelope kernel into the D row matrices, the existing multi_aggregate over
+// each matrix, every output compacted, one synchronisation.
+otsdb_status panel_shared(otsdb_ctx* c, const otsdb_query_spec* spec,
+                          const PanelReq& q, const otsdb_batch* b,
+                          std::vector<int64_t>& goff, const Params& P,
+                          std::vector<PanelFunc*>& E, PanelOutcome& O) {
+  hipStream_t st = c->stream;
+  const int D = (int)E.size();
+  BatchDev B{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
+             b->series_float};
+  std::vector<MultiState> MS((size_t)D);
+  std::vector<otsdb_query_spec> sp((size_t)D, *spec);
+  std::vector<MultiReq> qs((size_t)D);
+  std::vector<int> orig;
+  std::vector<otsdb_result> outs;
+  for (int d = 0; d < D; ++d) {
+    sp[d].ds_agg_id = E[d]->ds;
+    qs[d] = E[d]->req(q, (int)orig.size());
+    sp[d].agg_id = qs[d].aggs[0];
+    for (size_t j = 0; j < E[d]->idx.size(); ++j) {
+      orig.push_back(E[d]->idx[j]);
+      outs.push_back(E[d]->outs[j]);
+    }
+  }
+  otsdb_status rc;
+  size_t total = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 1) {
+      rc = ensure(&c->ws, &c->ws_cap, total);
+      if (rc) return rc;
+    }
+    size_t off = 0;
+    for (int d = 0; d < D; ++d) {
+      PanelPart part{off, 0, pass == 0};
+      rc = multi_build(c, &sp[d], qs[d], B, b->group_members, goff, P, nullptr,
+                       nullptr, MS[d], false, &part);
+      if (rc) return rc;
+      off += (part.ws_need + 255) & ~(size_t)255;
+    }
+    total = off;
+  }
+  HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(int), st));
+  HIP_TRY(hipMemsetAsync(c->d_merr, 0, OTSDB_MULTI_MAX * sizeof(int), st));
+  c->clean_entry = false;
+  c->n_multi_ds = c->n_multi_group = c->n_multi_kt = c->n_multi_tf = 0;
+  // ---- prep.  Bounds, seek and the first / last bucket do not depend on
+  // the function: one launch, shared by every function's work set.  Only
+  // under NONE fill k_prep also downsamples the bucket past the window with
+  // its monoid (SeriesMeta.of_val, what the rows interpolate toward): there
+  // each function runs its own k_prep — S threads, no pass over the stream.
+  const Params& Pr = MS[0].P;
+  uint32_t fn = 0;
+  PanelRows R{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  {
+    StageTimer tm(c, 3);
+    if (Pr.fill == 0 && !Pr.run_all) {
+      for (int d = 0; d < D; ++d) {
+        DsLaunch a = ds_args(c, Pr, B, MS[d].W);
+        with_monoid(E[d]->ds, [&](auto tag) {
+          launch_ds<decltype(tag)>(DS_PREP, a);
+        });
+      }
+    } else {
+      launch_ds<MSum<3>>(DS_PREP, ds_args(c, Pr, B, MS[0].W));
+      for (int d = 1; d < D; ++d) MS[d].W.SM = MS[0].W.SM;
+    }
+  }
+  for (int d = 0; d < D; ++d) {
+    double* v = MS[d].W.R.val;
+    switch (E[d]->fn) {
+      case PF_SUM: R.sum = v; break;
+      case PF_AVG: R.avg = v; break;
+      case PF_CNT: R.cnt = v; break;
+      case PF_MIN: R.min = v; break;
+      default: R.max = v; break;
+    }
+    fn |= E[d]->fn;
+  }
+  R.fn = fn;
+  {
+    StageTimer tm(c, 0);
+    launch_panel(st, Pr, B, MS[0].W.SM, R);
+  }
+  HIP_TRY(hipGetLastError());
+  ++c->n_multi_ds;
+  ++c->n_panel_passes;
+  c->n_panel_mats += D;
+  for (int d = 0; d < D; ++d) {
+    rc = multi_aggregate(c, MS[d], /*compact_now=*/false);
+    if (rc) return rc;
+  }
+  for (int d = 0; d < D; ++d) {
+    rc = multi_compact_launch(c, qs[d], MS[d].P, MS[d].G, MS[d].out_val,
+                              MS[d].out_emit);
+    if (rc) return rc;
+  }
+  const MultiReq all{(int32_t)orig.size(), nullptr, nullptr, outs.data()};
+  rc = multi_compact_wait(c, all, orig.data());
+  for (size_t j = 0; j < orig.size(); ++j)
+    O.total[orig[j]] = c->multi_total[orig[j]];
+  if (rc) O.fail_at(c, c->multi_failed, rc);
+  return OTSDB_OK;
+}
+
+otsdb_status run_panel_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
+                            const PanelReq& q, const otsdb_batch* b,
+                            std::vector<int64_t>& goff) {
+  c->multi_failed = -1;
+  c->n_panel_passes = c->n_panel_mats = 0;
+  std::vector<PanelFunc> F = panel_funcs(spec, q);
+  PanelOutcome O;
+  // ---- the shared pass: two or more envelope functions of a downsampled,
+  // columnar query without rate or per-series anchors, within the budgets
+  std::vector<PanelFunc*> E;
+  for (PanelFunc& f : F)
+    if (f.fn) E.push_back(&f);
+  bool shared = E.size() >= 2 && !spec->rate && !anchored(spec) &&
+                !((((uintptr_t)b->ts_ms) | ((uintptr_t)b->val)) & 15);
+  Params P;
+  if (shared) {
+    const otsdb_query_spec s0 = panel_spec(spec, q, E[0]->idx[0]);
+    shared = make_params(&s0, &P, c) == OTSDB_OK;  // (else: the calls report it)
+  }
+  for (size_t d = 0; shared && d < E.size(); ++d) {
+    otsdb_query_spec sd = *spec;
+    sd.ds_agg_id = E[d]->ds;
+    shared = multi_shares_rows(&sd, E[d]->req(q, 0), P, b->n_series, goff, 1,
+                               (int)E.size());
+  }
+  if (shared) {
+    const otsdb_status rc = panel_shared(c, spec, q, b, goff, P, E, O);
+    if (rc) return rc;  // (the device or the workspace, not an output)
+  }
+  // ---- everything else function by function: one multi call each
+  for (PanelFunc& f : F) {
+    if (shared && f.fn) continue;
+    otsdb_query_spec sf = *spec;
+    sf.ds_agg_id = f.ds;
+    c->result_short = false;
+    const otsdb_status rc = run_multi_impl(c, &sf, f.req(q, 0), b, goff);
+    c->n_panel_passes += c->n_multi_ds;
+    c->n_panel_mats += c->n_multi_ds;
+    if (rc) {
+      const int j = c->multi_failed >= 0 ? c->multi_failed : 0;
+      O.fail_at(c, f.idx[(size_t)j], rc);
+      continue;
+    }
+    for (size_t j = 0; j < f.idx.size(); ++j)
+      O.total[f.idx[j]] = c->multi_total[j];
+  }
+  for (int i = 0; i < q.n; ++i) c->multi_total[i] = O.total[i];
+  if (O.failed < 0) return OTSDB_OK;
+  c->multi_failed = O.failed;
+  c->result_short = O.result_short;
+  g_last_error = O.msg;
+  return O.rc;
 }
 
 // otsdb_decode_cells_device without the lock (also the fallback of the
@@ -3430,11 +3761,13 @@ otsdb_status otsdb_agg_run_cells_device(otsdb_ctx* c,
   return rc;
 }
 
-// The host-pointer entries: the batch staged in HBM once, n results (mq: the
-// multi-aggregator request whose results `outs` are, else one single query).
+// The host-pointer entries: the batch staged in HBM once, n results (mq / pq:
+// the multi-aggregator / panel request whose results `outs` are, else one
+// single query).
 static otsdb_status run_host(otsdb_ctx* c, const otsdb_query_spec* spec,
                              const otsdb_batch* b, int n, otsdb_result* outs,
-                             const MultiReq* mq) {
+                             const MultiReq* mq,
+                             const PanelReq* pq = nullptr) {
   CtxLock lk(c);
   HIP_TRY(hipSetDevice(c->device));
   std::vector<int64_t> goff;
@@ -3501,7 +3834,12 @@ static otsdb_status run_host(otsdb_ctx* c, const otsdb_query_spec* spec,
     dr[i].is_int = (uint8_t*)pp[10 + 4 * i];
   }
   c->result_short = false;
-  if (mq) {
+  const bool many = mq || pq;
+  if (pq) {
+    PanelReq dq = *pq;
+    dq.outs = dr.data();
+    rc = run_panel_impl(c, spec, dq, &db, goff);
+  } else if (mq) {
     MultiReq dq = *mq;
     dq.outs = dr.data();
     rc = run_multi_impl(c, spec, dq, &db, goff);
@@ -3510,14 +3848,14 @@ static otsdb_status run_host(otsdb_ctx* c, const otsdb_query_spec* spec,
   }
   if (rc == OTSDB_E_CAPACITY && c->result_short) {
     // the offsets of the result too small (and of those before it) are whole
-    const int last = mq ? c->multi_failed : 0;
+    const int last = many ? c->multi_failed : 0;
     for (int i = 0; i < last; ++i)
       copy_offsets_back(c, &outs[i], dr[i].offsets, G, rc);
     return copy_offsets_back(c, &outs[last], dr[last].offsets, G, rc);
   }
   if (rc) return rc;
   for (int i = 0; i < n; ++i) {
-    const int64_t total = mq ? c->multi_total[i] : c->h_small[1];
+    const int64_t total = many ? c->multi_total[i] : c->h_small[1];
     otsdb_result* out = &outs[i];
     HIP_TRY(hipMemcpyAsync(out->offsets, dr[i].offsets, 8 * (G + 1),
                            hipMemcpyDeviceToHost, st));
@@ -3588,6 +3926,63 @@ otsdb_status otsdb_agg_run_multi(otsdb_ctx* c, const otsdb_query_spec* spec,
   const otsdb_status rc = check_multi(spec, q);
   if (rc) return rc;
   return run_host(c, spec, b, n_out, outs, &q);
+}
+
+otsdb_status otsdb_agg_plan_panel(otsdb_ctx* c, const otsdb_query_spec* spec,
+                                  int32_t n_out, const int32_t* ds_agg_ids,
+                                  const int32_t* agg_ids,
+                                  const int32_t* interps, const otsdb_batch* b,
+                                  otsdb_sizes* out) {
+  if (!spec || !b || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  const PanelReq q{n_out, ds_agg_ids, agg_ids, interps, nullptr};
+  otsdb_status rc = check_panel(spec, q);
+  if (rc) return rc;
+  const otsdb_query_spec s0 = panel_spec(spec, q, 0);
+  rc = otsdb_agg_plan(c, &s0, b, out);
+  if (rc) return rc;
+  // the bound of the point count holds for each output; the workspace: per
+  // distinct function what plan_multi counts for its outputs (at most n_out
+  // functions of one output each)
+  if (s0.ds_interval_ms > 0 || s0.run_all)
+    out->workspace_bytes =
+        (int64_t)n_out *
+        (b->n_series * (out->n_buckets * 18 + 48) +
+         (int64_t)2 * b->n_groups * (out->n_buckets * 9 + 8) +
+         (int64_t)kMultiSlots * (b->n_series / kChunk + b->n_groups) *
+             out->n_buckets * 33);
+  return OTSDB_OK;
+}
+
+otsdb_status otsdb_agg_run_panel_device(otsdb_ctx* c,
+                                        const otsdb_query_spec* spec,
+                                        int32_t n_out,
+                                        const int32_t* ds_agg_ids,
+                                        const int32_t* agg_ids,
+                                        const int32_t* interps,
+                                        const otsdb_batch* b,
+                                        otsdb_result* outs, void* hip_stream) {
+  if (!c || !spec || !b || !outs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  const PanelReq q{n_out, ds_agg_ids, agg_ids, interps, outs};
+  otsdb_status rc = check_panel(spec, q);
+  if (rc) return rc;
+  CtxLock lk(c);
+  HIP_TRY(hipSetDevice(c->device));
+  StreamBinding bind(c, hip_stream);
+  std::vector<int64_t> goff;
+  rc = read_goff(c, b, true, goff);
+  if (!rc) rc = run_panel_impl(c, spec, q, b, goff);
+  return rc;
+}
+
+otsdb_status otsdb_agg_run_panel(otsdb_ctx* c, const otsdb_query_spec* spec,
+                                 int32_t n_out, const int32_t* ds_agg_ids,
+                                 const int32_t* agg_ids, const int32_t* interps,
+                                 const otsdb_batch* b, otsdb_result* outs) {
+  if (!c || !spec || !b || !outs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  const PanelReq q{n_out, ds_agg_ids, agg_ids, interps, outs};
+  const otsdb_status rc = check_panel(spec, q);
+  if (rc) return rc;
+  return run_host(c, spec, b, n_out, outs, nullptr, &q);
 }
 
 otsdb_status otsdb_agg_run_cells_multi_device(
@@ -4559,11 +4954,12 @@ otsdb_status otsdb_prof_read(otsdb_ctx* c, double* ms, int64_t* launches,
 otsdb_status otsdb_ctx_counters(otsdb_ctx* c, int64_t* out, int n) {
   if (!c || (n > 0 && !out)) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
   CtxLock lk(c, /*keep_session=*/true);
-  const int64_t v[10] = {c->n_cells_uniform, c->n_cells_general,
+  const int64_t v[12] = {c->n_cells_uniform, c->n_cells_general,
                          c->n_cells_uni_miss, c->sel.key_reads, c->sel.passes,
                          c->n_multi_ds,       c->n_multi_group, c->n_multi_kt,
-                         c->n_multi_tf,       c->sel.sessions};
-  for (int i = 0; i < n && i < 10; ++i) out[i] = v[i];
+                         c->n_multi_tf,       c->sel.sessions,
+                         c->n_panel_passes,   c->n_panel_mats};
+  for (int i = 0; i < n && i < 12; ++i) out[i] = v[i];
   return OTSDB_OK;
 }
 

@@ -449,9 +449,27 @@ struct RowSink {
     if (direct) rowv[k] = v;
     else rv[k & mask] = v;
   }
+  // a closed run: its state's one finished value.  (The panel sink, panel.hip,
+  // writes several rows from one state; the reduction below names the sink
+  // only through close / drain / absent / clear.)
+  template <class M>
+  DEV void close(int k, const M& m, int& err) { put(k, m.finish(&err)); }
+  DEV void drain(int64_t b);   // ring slot of final bucket b -> the row
+  DEV void absent(int64_t b);  // bucket b of the row: absent
+  DEV void clear(int i);       // ring slot i: absent
 };
 
 DEV double absent_value() { return __longlong_as_double(kAbsentBits); }
+
+DEV void RowSink::drain(int64_t b) {
+  const int i = (int)(b & mask);
+  const double v = rv[i];
+  if (nt) __builtin_nontemporal_store(v, &rowv[b]);
+  else if (!nostore || v == 1234.5678) rowv[b] = v;  // ablation
+  rv[i] = absent_value();
+}
+DEV void RowSink::absent(int64_t b) { rowv[b] = absent_value(); }
+DEV void RowSink::clear(int i) { rv[i] = absent_value(); }
 
 // RateSpan over a series' bucket points, carried across ring flushes
 // (k_transform's two passes, transform_rate, folded into the flush of each
@@ -569,26 +587,21 @@ DEV void rate_flush(const Params& P, RowSink& S, RateState& R, int64_t f,
 }
 
 // drains the ring's buckets [flushed, limit) (all final) to the row
-template <int RATE = 0>
-DEV void sink_flush(RowSink& S, int64_t& flushed, int64_t limit,
+template <int RATE = 0, class SK = RowSink>
+DEV void sink_flush(SK& S, int64_t& flushed, int64_t limit,
                     const Params* P = nullptr, RateState* R = nullptr) {
   const int lane = LANE;
-  if (RATE) {
+  if constexpr (RATE != 0) {
     for (int64_t f = flushed; f < limit; f += 64) rate_flush(*P, S, *R, f, limit);
     if (limit > flushed) flushed = limit;
     return;
-  }
-  for (int64_t f = flushed; f < limit; f += 64) {
-    const int64_t b = f + lane;
-    if (b < limit) {
-      const int i = (int)(b & S.mask);
-      const double v = S.rv[i];
-      if (S.nt) __builtin_nontemporal_store(v, &S.rowv[b]);
-      else if (!S.nostore || v == 1234.5678) S.rowv[b] = v;  // ablation
-      S.rv[i] = absent_value();
+  } else {
+    for (int64_t f = flushed; f < limit; f += 64) {
+      const int64_t b = f + lane;
+      if (b < limit) S.drain(b);
     }
+    if (limit > flushed) flushed = limit;
   }
-  if (limit > flushed) flushed = limit;
 }
 
 // Fast lane fold for lanes whose K points fall into at most three adjacent
@@ -603,9 +616,10 @@ DEV void sink_flush(RowSink& S, int64_t& flushed, int64_t limit,
 // spans four or more buckets.
 // nv < K: only the first nv points are in range (the step reaches past the
 // end of the series / window); nv == 0 leaves the lane empty (nseg = 0).
-template <class M, int K, bool FLOATONLY, class TT = int64_t>
+template <class M, int K, bool FLOATONLY, class TT = int64_t,
+          class SK = RowSink>
 DEV bool fold_fast(const Params& P, const BatchDev& B, int sf, int64_t i0,
-                   const TT* t, const int64_t* v, RowSink& S, int& err,
+                   const TT* t, const int64_t* v, SK& S, int& err,
                    int& nseg, int& cur_key, int& head_key, M& cur, M& head,
                    int nv = K) {
   if (nv <= 0) {
@@ -662,7 +676,7 @@ DEV bool fold_fast(const Params& P, const BatchDev& B, int sf, int64_t i0,
   } else {
     nseg = any_mid ? 3 : 2;
     head = h;
-    if (any_mid) S.put(k0 + 1, m.finish(&err));
+    if (any_mid) S.close(k0 + 1, m, err);
   }
   return true;
 }
@@ -670,10 +684,11 @@ DEV bool fold_fast(const Params& P, const BatchDev& B, int sf, int64_t i0,
 // Folds the K points of one lane in order: the first run (which may continue
 // from the previous lane) goes to `head`, the last run (which may continue
 // into the next lane) stays in `cur`, runs in between close here.
-template <class M, int K, bool FLOATONLY, bool CHECKED, class TT = int64_t>
+template <class M, int K, bool FLOATONLY, bool CHECKED, class TT = int64_t,
+          class SK = RowSink>
 DEV void fold_lane(const Params& P, const BatchDev& B, int sf, int64_t i0,
                    int64_t lo, int64_t hi, const TT* t, const int64_t* v,
-                   RowSink& S, int& err, int& nseg,
+                   SK& S, int& err, int& nseg,
                    int& cur_key, int& head_key, M& cur, M& head) {
   TT bnd = tmin<TT>();  // first timestamp past cur_key's bucket
 #pragma unroll
@@ -697,7 +712,7 @@ DEV void fold_lane(const Params& P, const BatchDev& B, int sf, int64_t i0,
         head_key = cur_key;
         head = cur;
       } else {  // a bucket wholly inside this lane
-        S.put(cur_key, cur.finish(&err));
+        S.close(cur_key, cur, err);
       }
       cur_key = k;
       cur = M::from(x);
@@ -807,10 +822,11 @@ DEV void ordered_step(const Params& P, const BatchDev& B, int sf, int64_t lo,
 // FO = 1: the caller guarantees doubles only (the cells fold decodes every
 // value to its double bits): the per-point type tests and their registers
 // are not compiled in
-template <class M, int K, int DPP, class TT = int64_t, int FO = 0>
+template <class M, int K, int DPP, class TT = int64_t, int FO = 0,
+          class SK = RowSink>
 DEV void reduce_step(const Params& P, const BatchDev& B, int sf, int64_t lo,
                      int64_t hi, int64_t base, int64_t i0, const TT* t,
-                     const int64_t* v, RowSink& S, int& err,
+                     const int64_t* v, SK& S, int& err,
                      int& carry_key, M& carry, bool keep_open = false) {
   constexpr int PTS = 64 * K;
   const int lane = LANE;
@@ -856,7 +872,7 @@ DEV void reduce_step(const Params& P, const BatchDev& B, int sf, int64_t lo,
 #if defined(OTSDB_REDUCE_ABL) && OTSDB_REDUCE_ABL == 1  // timing: lane fold only
   {
     const double x = cur.finish(&err) + head.finish(&err);
-    if (x == 1234.5678) S.put(cur_key, x);
+    if (x == 1234.5678) S.close(cur_key, cur, err);
     carry_key = __builtin_amdgcn_readlane(cur_key, 63);
     return;
   }
@@ -894,7 +910,7 @@ DEV void reduce_step(const Params& P, const BatchDev& B, int sf, int64_t lo,
       if (nseg == 1) cur = M::combine(carry, cur);
       else head = M::combine(carry, head);
     } else if (carry_key >= 0 && carry_key < P.nb) {
-      S.put(carry_key, carry.finish(&err));
+      S.close(carry_key, carry, err);
     }
   }
   // ---- segmented inclusive scan over the lanes' tail runs
@@ -944,15 +960,15 @@ DEV void reduce_step(const Params& P, const BatchDev& B, int sf, int64_t lo,
     if (__ballot(put_head && put_tail) == 0) {
       if (put_head || put_tail) {
         const M& r = put_head ? hfull : st;
-        S.put(put_head ? head_key : key, r.finish(&err));
+        S.close(put_head ? head_key : key, r, err);
       }
     } else {
-      if (put_head) S.put(head_key, hfull.finish(&err));
-      if (put_tail) S.put(key, st.finish(&err));
+      if (put_head) S.close(head_key, hfull, err);
+      if (put_tail) S.close(key, st, err);
     }
   } else {
-    if (put_head) S.put(head_key, hfull.finish(&err));
-    if (put_tail) S.put(key, st.finish(&err));
+    if (put_head) S.close(head_key, hfull, err);
+    if (put_tail) S.close(key, st, err);
   }
   Packed p = st.pack();
   if (DPP) {
@@ -984,8 +1000,8 @@ DEV int64_t step_last_key(const Params& P, const BatchDev& B, int64_t base,
 
 // returns true (RATE: nothing written) when the step spans more buckets
 // than the ring holds
-template <int WIN, int K, int RATE = 0>
-DEV bool ring_before(const Params& P, const BatchDev& B, RowSink& S,
+template <int WIN, int K, int RATE = 0, class SK = RowSink>
+DEV bool ring_before(const Params& P, const BatchDev& B, SK& S,
                      int64_t& flushed, int64_t lo, int64_t hi, int64_t base,
                      const int64_t* t, int carry_key, RateState* R = nullptr) {
   if (WIN == 0) return false;
@@ -1007,7 +1023,7 @@ DEV bool ring_before(const Params& P, const BatchDev& B, RowSink& S,
       // absent, then let the step store straight to HBM behind it
       const int lane = LANE;
       for (int64_t f = flushed; f <= k_hi; f += 64)
-        if (f + lane <= k_hi) S.rowv[f + lane] = absent_value();
+        if (f + lane <= k_hi) S.absent(f + lane);
       wait_vmcnt(0);
       S.direct = 1;
     }
@@ -1015,8 +1031,8 @@ DEV bool ring_before(const Params& P, const BatchDev& B, RowSink& S,
   return false;
 }
 
-template <int WIN, int FL, int RATE = 0>
-DEV void ring_after(const Params& P, const BatchDev& B, RowSink& S,
+template <int WIN, int FL, int RATE = 0, class SK = RowSink>
+DEV void ring_after(const Params& P, const BatchDev& B, SK& S,
                     int64_t& flushed, int64_t hi, int64_t base, int64_t pts,
                     int carry_key, RateState* R = nullptr) {
   if (WIN == 0) return;
@@ -1100,10 +1116,9 @@ DEV void rate_finish(const Params& P, const SeriesMeta& SM, int64_t s,
 // One series (wavefront) of k_bucketize_k: S says where its closed buckets
 // go (row, LDS ring, or k_bucketize_group's group row).
 template <class M, int K, int PF, int NT, int ABL, int DPP, int WIN, int FL,
-          int RATE>
+          int RATE, class SK = RowSink>
 DEV void bucketize_series(const Params& P, const BatchDev& B,
-                          const SeriesMeta& SM, RowSink& S, double* ring,
-                          int64_t s) {
+                          const SeriesMeta& SM, SK& S, int64_t s) {
   static_assert(K % 2 == 0, "K must be even (16-byte loads)");
   static_assert((WIN & (WIN - 1)) == 0, "WIN: power of two");
   static_assert(!RATE || WIN > 0, "RATE needs the ring");
@@ -1112,7 +1127,7 @@ DEV void bucketize_series(const Params& P, const BatchDev& B,
   const int64_t hi = SM.keep[s] ? SM.hi[s] : 0;
   RateState RS{P.rate_origin_ts, P.rate_origin_val, -1, 0.0, -1, -1, 0.0, 0, 0};
   if (lo >= hi) {
-    if (RATE) {  // absent, or its rates past the window held (rate_finish)
+    if constexpr (RATE != 0) {  // absent, or its rates past the window held (rate_finish)
       rate_finish(P, SM, s, S, RS, -1);
       if (lane == 0) P.redo[s] = 0;
     }
@@ -1121,7 +1136,7 @@ DEV void bucketize_series(const Params& P, const BatchDev& B,
   const int sf = B.series_float ? (int)B.series_float[s] : 1;
   int64_t flushed = 0;
   if (WIN) {
-    for (int i = lane; i < WIN; i += 64) ring[i] = absent_value();
+    for (int i = lane; i < WIN; i += 64) S.clear(i);
     flushed = bucket_of(P, B.ts[lo]);
   }
   int err = 0;
@@ -1177,7 +1192,7 @@ DEV void bucketize_series(const Params& P, const BatchDev& B,
         pv_.touch(B.val + i0 + OTSDB_PF_BUCK * PTS);
       }
     }
-    if (ABL == 1) {  // tuning ablation: stream only
+    if constexpr (ABL == 1) {  // tuning ablation: stream only
       int64_t x = 0;
 #pragma unroll
       for (int j = 0; j < K; ++j) x ^= t[j] + v[j];
@@ -1203,13 +1218,13 @@ DEV void bucketize_series(const Params& P, const BatchDev& B,
     return;
   }
   if (carry_key >= 0 && carry_key < P.nb && lane == 0)
-    S.put(carry_key, carry.finish(&err));
+    S.close(carry_key, carry, err);
   // every bucket from the first point's to the last point's is written; a
   // last step that went direct already stored its buckets behind `flushed`
   // (the ring only holds absent slots there)
   const int64_t k_last = bucket_of(P, B.ts[hi - 1]);
   if (WIN && !S.direct) sink_flush<RATE>(S, flushed, k_last + 1, &P, &RS);
-  if (RATE) {
+  if constexpr (RATE != 0) {
     if (RS.bad) {
       if (lane == 0) P.redo[s] = 1;
       return;
@@ -1233,8 +1248,7 @@ __global__ __launch_bounds__(256, WAVES) void k_bucketize_k(Params P,
   if (P.only_redo && !P.redo[s]) return;
   RowSink S{R.val + s * P.nb, R.state + s * P.nb, ring_v[w], WS - 1,
             WIN == 0, WIN == 0, ABL == 2, NT == 2};
-  bucketize_series<M, K, PF, NT, ABL, DPP, WIN, FL, RATE>(P, B, SM, S,
-                                                          ring_v[w], s);
+  bucketize_series<M, K, PF, NT, ABL, DPP, WIN, FL, RATE>(P, B, SM, S, s);
 }
 
 // ------------------------------------------------------------------------

@@ -1,0 +1,195 @@
+// panel.hip — panel queries: several downsampling functions over one pass of
+// the point stream (otsdb_agg_run_panel*).
+//
+// k_bucketize_panel is the production ring kernel (k_bucketize_k<M, 8, ...,
+// DPP = 1, WIN = OTSDB_RING_WIN>) over one combined state, the envelope
+// MEnv = {sum, count, min, max}: bucketize_series / reduce_step run unchanged
+// — 8 points a lane through fold_fast / fold_lane, the carry between steps,
+// the DPP segmented scan with its run-length skipping, one close per run —
+// and the sink writes up to five rows from each closed state (sum, avg,
+// count, min, max), each through its own per-wavefront LDS ring.  Every
+// component of MEnv is MSum<0|1|3> / MMinMax<false|true> operation for
+// operation, in the same order, so row i is bit for bit the row
+// k_bucketize_k<M_i> writes.  (Included by engine.hip after kernels.hip.)
+#ifndef OTSDB_RING_WIN
+#define OTSDB_RING_WIN 256
+#endif
+#ifndef OTSDB_RING_FL
+#define OTSDB_RING_FL 64
+#endif
+
+namespace otsdb {
+
+// the rows a panel pass can write; a request's set is a kernel-uniform mask
+enum : uint32_t {
+  PF_SUM = 1,  // sum / zimsum / pfsum
+  PF_AVG = 2,
+  PF_CNT = 4,
+  PF_MIN = 8,  // min / mimmin
+  PF_MAX = 16  // max / mimmax
+};
+constexpr int kPanelFns = 5;
+
+// ---------------------------------------------------------------- envelope
+// MSum<0|1|3> (s, n) and MMinMax<false|true> (mn, mx) side by side.
+struct MEnv {
+  static constexpr bool kOrdered = false;
+  static constexpr bool kCostlyFinish = true;  // avg: s / n
+  double s;
+  int32_t n;
+  double mn, mx;
+  DEV static MEnv init() {
+    return {0.0, 0, __builtin_inf(), -__builtin_inf()};
+  }
+  DEV static MEnv from(double v) {
+    if (is_nan(v)) return init();
+    return {0.0 + v, 1, v, v};
+  }
+  DEV void push(double v) {
+    if (!is_nan(v)) {
+      s += v;
+      ++n;
+      if (v < mn) mn = v;
+      if (v > mx) mx = v;
+    }
+  }
+  DEV void push_if(bool mk, double v) {  // branch free; NaN compares false
+    const bool ok = mk & !is_nan(v);
+    s += ok ? v : 0.0;
+    n += ok ? 1 : 0;
+    mn = (mk & (v < mn)) ? v : mn;
+    mx = (mk & (v > mx)) ? v : mx;
+  }
+  DEV static MEnv combine(const MEnv& a, const MEnv& b) {
+    return {a.s + b.s, a.n + b.n, b.mn < a.mn ? b.mn : a.mn,  // the earliest
+            b.mx > a.mx ? b.mx : a.mx};                       // extreme stays
+  }
+  DEV double sum() const { return n == 0 ? qnan() : s; }
+  DEV double avg() const { return n == 0 ? qnan() : s / (double)(int32_t)n; }
+  DEV double count() const { return (double)n; }
+  DEV double min() const { return mn == __builtin_inf() ? qnan() : mn; }
+  DEV double max() const { return mx == -__builtin_inf() ? qnan() : mx; }
+  DEV Packed pack() const { return {s, mn, mx, n}; }
+  DEV static MEnv unpack(const Packed& p) {
+    return {p.x, (int32_t)p.w, p.y, p.z};
+  }
+  DEV void shfl_up(int d) {
+    s = __shfl_up(s, d);
+    n = __shfl_up(n, d);
+    mn = __shfl_up(mn, d);
+    mx = __shfl_up(mx, d);
+  }
+  template <int CTRL, int RM>
+  DEV void dpp() {
+    s = dppv<CTRL, RM>(s);
+    n = dppv<CTRL, RM>(n);
+    mn = dppv<CTRL, RM>(mn);
+    mx = dppv<CTRL, RM>(mx);
+  }
+};
+
+// the row matrices of one panel pass ([S * nb] each; null where fn has no bit)
+struct PanelRows {
+  double *sum, *avg, *cnt, *min, *max;
+  uint32_t fn;
+};
+
+// RowSink's ring form for up to five rows: one series row and one LDS ring
+// per function of the mask (values only: sentinel rows, no state bytes)
+struct PanelSink {
+  double *row_sum, *row_avg, *row_cnt, *row_min, *row_max;
+  double *rg_sum, *rg_avg, *rg_cnt, *rg_min, *rg_max;
+  uint32_t fn;  // kernel-uniform
+  int mask;     // WIN - 1
+  int direct;   // wave-uniform: write straight to HBM this step
+  DEV void put1(double* rowv, double* rv, int k, double v) const {
+    v = is_nan(v) ? qnan() : v;  // never the absent pattern
+    if (direct) rowv[k] = v;
+    else rv[k & mask] = v;
+  }
+  DEV void close(int k, const MEnv& m, int& err) {
+    if (fn & PF_SUM) put1(row_sum, rg_sum, k, m.sum());
+    if (fn & PF_AVG) put1(row_avg, rg_avg, k, m.avg());
+    if (fn & PF_CNT) put1(row_cnt, rg_cnt, k, m.count());
+    if (fn & PF_MIN) put1(row_min, rg_min, k, m.min());
+    if (fn & PF_MAX) put1(row_max, rg_max, k, m.max());
+  }
+  DEV static void drain1(double* rowv, double* rv, int64_t b, int i) {
+    rowv[b] = rv[i];
+    rv[i] = absent_value();
+  }
+  DEV void drain(int64_t b) {
+    const int i = (int)(b & mask);
+    if (fn & PF_SUM) drain1(row_sum, rg_sum, b, i);
+    if (fn & PF_AVG) drain1(row_avg, rg_avg, b, i);
+    if (fn & PF_CNT) drain1(row_cnt, rg_cnt, b, i);
+    if (fn & PF_MIN) drain1(row_min, rg_min, b, i);
+    if (fn & PF_MAX) drain1(row_max, rg_max, b, i);
+  }
+  DEV void absent(int64_t b) {
+    if (fn & PF_SUM) row_sum[b] = absent_value();
+    if (fn & PF_AVG) row_avg[b] = absent_value();
+    if (fn & PF_CNT) row_cnt[b] = absent_value();
+    if (fn & PF_MIN) row_min[b] = absent_value();
+    if (fn & PF_MAX) row_max[b] = absent_value();
+  }
+  DEV void clear(int i) {
+    if (fn & PF_SUM) rg_sum[i] = absent_value();
+    if (fn & PF_AVG) rg_avg[i] = absent_value();
+    if (fn & PF_CNT) rg_cnt[i] = absent_value();
+    if (fn & PF_MIN) rg_min[i] = absent_value();
+    if (fn & PF_MAX) rg_max[i] = absent_value();
+  }
+};
+
+// One wavefront per series, four a workgroup.  Dynamic LDS: D rings of WIN
+// doubles per wavefront, D the functions of the mask (panel_lds_bytes): 16 KB
+// a workgroup for two functions, 24 KB for min / avg / max, 40 KB for all
+// five — 10, 6 and 4 workgroups a CU by LDS (160 KB).
+template <int WIN, int FL>
+__global__ __launch_bounds__(256) void k_bucketize_panel(Params P, BatchDev B,
+                                                         SeriesMeta SM,
+                                                         PanelRows R) {
+  extern __shared__ double panel_ring[];
+  const int w = threadIdx.x >> 6;
+  const int64_t s = (int64_t)blockIdx.x * 4 + w;
+  if (s >= B.S) return;
+  const int D = __popc(R.fn);
+  double* ring = panel_ring + (size_t)w * D * WIN;
+  const int64_t row = s * P.nb;
+  PanelSink S;
+  S.fn = R.fn;
+  S.mask = WIN - 1;
+  S.direct = 0;
+  // ring r of this wavefront goes to the r-th function of the mask
+  int r = 0;
+  S.row_sum = R.sum + row;
+  S.rg_sum = ring + r * WIN;
+  r += (R.fn & PF_SUM) ? 1 : 0;
+  S.row_avg = R.avg + row;
+  S.rg_avg = ring + r * WIN;
+  r += (R.fn & PF_AVG) ? 1 : 0;
+  S.row_cnt = R.cnt + row;
+  S.rg_cnt = ring + r * WIN;
+  r += (R.fn & PF_CNT) ? 1 : 0;
+  S.row_min = R.min + row;
+  S.rg_min = ring + r * WIN;
+  r += (R.fn & PF_MIN) ? 1 : 0;
+  S.row_max = R.max + row;
+  S.rg_max = ring + r * WIN;
+  bucketize_series<MEnv, 8, 0, 0, 0, 1, WIN, FL, 0>(P, B, SM, S, s);
+}
+
+inline size_t panel_lds_bytes(uint32_t fn) {
+  return (size_t)__builtin_popcount(fn) * 4 * OTSDB_RING_WIN * sizeof(double);
+}
+
+inline void launch_panel(hipStream_t st, const Params& P, const BatchDev& B,
+                         const SeriesMeta& SM, const PanelRows& R) {
+  if (B.S <= 0 || !R.fn) return;
+  hipLaunchKernelGGL((k_bucketize_panel<OTSDB_RING_WIN, OTSDB_RING_FL>),
+                     dim3((unsigned)((B.S + 3) / 4)), dim3(256),
+                     (unsigned)panel_lds_bytes(R.fn), st, P, B, SM, R);
+}
+
+}  // namespace otsdb

@@ -129,6 +129,31 @@ def multi_args(aggs, interps=None):
     return len(aggs), ids, it
 
 
+def panel_args(queries):
+    """The queries of a panel call as the C-ABI takes them: (n_out, int32
+    downsampling function ids, int32 aggregator ids, int32 interpolations).
+    `queries`: (aggregator, downsampling function[, interpolation]) each, the
+    functions given as multi_args takes aggregators, the interpolation None
+    for the aggregator's own.  Checked before anything touches the device."""
+    queries = [tuple(q) for q in queries]
+    if not 1 <= len(queries) <= abi.MULTI_MAX:
+        raise IllegalArgumentException(
+            "%d queries: a panel call takes 1 to %d"
+            % (len(queries), abi.MULTI_MAX))
+    for q in queries:
+        if len(q) not in (2, 3):
+            raise IllegalArgumentException(
+                "a panel query is (aggregator, downsampling function"
+                "[, interpolation]): %r" % (q,))
+    n, ids, it = multi_args([q[0] for q in queries],
+                            [q[2] if len(q) == 3 else None for q in queries])
+    _, ds, _ = multi_args([q[1] for q in queries])
+    if (ds == Aggregators.NONE.id).any():
+        raise IllegalArgumentException(
+            "cannot use the NONE aggregator for downsampling")
+    return n, ds, ids, it
+
+
 class Engine:
     """One context per GPU (one process per GPU)."""
 
@@ -158,6 +183,14 @@ class Engine:
         self._check(self.lib.otsdb_ctx_counters(self.ctx, out, 9))
         return dict(downsample_passes=out[5], group_passes=out[6],
                     key_transposes=out[7], transform_passes=out[8])
+
+    def panel_counters(self):
+        """Of the last panel call (otsdb_ctx_counters [10..11]): passes over
+        the point stream (one for all envelope functions that share a pass,
+        one per multi call otherwise) and row matrices built."""
+        out = (C.c_int64 * 12)()
+        self._check(self.lib.otsdb_ctx_counters(self.ctx, out, 12))
+        return dict(point_stream_passes=out[10], row_matrices=out[11])
 
     def sel_sessions(self):
         """otsdb_ctx_counters [9]: otsdb_sel_* sessions prepared since the
@@ -236,6 +269,45 @@ class Engine:
         self._check(self.lib.otsdb_agg_run_multi(
             self.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
             C.byref(b), rs))
+        return [[DataPoints(ts[i, offs[i, g]:offs[i, g + 1]],
+                            bits[i, offs[i, g]:offs[i, g + 1]],
+                            isint[i, offs[i, g]:offs[i, g + 1]])
+                 for g in range(G)] for i in range(n)]
+
+    def plan_panel(self, spec, queries, batch):
+        n, ds, ids, it = panel_args(queries)
+        sz = abi.Sizes()
+        self._check(self.lib.otsdb_agg_plan_panel(
+            self.ctx, C.byref(spec), n, ds.ctypes.data, ids.ctypes.data,
+            it.ctypes.data, C.byref(batch.as_abi()), C.byref(sz)))
+        return sz
+
+    def run_panel(self, spec, queries, batch):
+        """The sub-queries of one panel over one pass of the point stream
+        (host arrays): `queries` is a list of (aggregator, downsampling
+        function[, interpolation]); `spec`'s own aggregator, downsampling
+        function and interpolation are ignored.  Returns one list of
+        DataPoints (one per group) per query, each what run() gives for that
+        query."""
+        n, ds, ids, it = panel_args(queries)
+        sz = abi.Sizes()
+        self._check(self.lib.otsdb_agg_plan_panel(
+            self.ctx, C.byref(spec), n, ds.ctypes.data, ids.ctypes.data,
+            it.ctypes.data, C.byref(batch.as_abi()), C.byref(sz)))
+        cap = max(1, int(sz.max_out_points))
+        G = batch.n_groups
+        offs = np.zeros((n, G + 1), np.int64)
+        ts = np.zeros((n, cap), np.int64)
+        bits = np.zeros((n, cap), np.int64)
+        isint = np.zeros((n, cap), np.uint8)
+        rs = (abi.Result * n)()
+        for i in range(n):
+            rs[i] = abi.Result(cap, offs[i].ctypes.data, ts[i].ctypes.data,
+                               bits[i].ctypes.data, isint[i].ctypes.data)
+        b = batch.as_abi()
+        self._check(self.lib.otsdb_agg_run_panel(
+            self.ctx, C.byref(spec), n, ds.ctypes.data, ids.ctypes.data,
+            it.ctypes.data, C.byref(b), rs))
         return [[DataPoints(ts[i, offs[i, g]:offs[i, g + 1]],
                             bits[i, offs[i, g]:offs[i, g + 1]],
                             isint[i, offs[i, g]:offs[i, g + 1]])
@@ -369,6 +441,26 @@ def run_multi_device(engine, spec, aggs, dbatch, dresults, stream=None,
     engine._check(engine.lib.otsdb_agg_run_multi_device(
         engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
         C.byref(b), rs, None if stream is None else C.c_void_p(stream)))
+
+
+def run_panel_device(engine, spec, queries, dbatch, dresults, stream=None):
+    """Device-resident panel call: dresults[i] (a DeviceResult) takes what
+    run_device gives for queries[i] = (aggregator, downsampling function
+    [, interpolation]); the envelope functions share one pass over the point
+    stream."""
+    n, ds, ids, it = panel_args(queries)
+    if len(dresults) != n:
+        raise IllegalArgumentException(
+            "%d results for %d queries" % (len(dresults), n))
+    b = _abi_cached(dbatch, _BATCH_TENSORS, dbatch.as_abi,
+                    dbatch.group_offsets._version)
+    rs = (abi.Result * n)()
+    for i, r in enumerate(dresults):
+        rs[i] = _abi_cached(r, _RESULT_TENSORS, r.as_abi, r.cap)
+    engine._check(engine.lib.otsdb_agg_run_panel_device(
+        engine.ctx, C.byref(spec), n, ds.ctypes.data, ids.ctypes.data,
+        it.ctypes.data, C.byref(b), rs,
+        None if stream is None else C.c_void_p(stream)))
 
 
 def partials_multi_device(engine, spec, aggs, dbatch, partials, emit,

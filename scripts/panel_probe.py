@@ -1,0 +1,163 @@
+"""Panel call (several downsampling functions over one pass of the point
+stream) against what a caller does without it: the same outputs as
+back-to-back otsdb_agg_run_device single queries on a library built from the
+PARENT commit, in the same process, on the BASELINE shapes.
+
+    python -m scripts.panel_probe --baseline-lib PATH/libotsdb_agg.so
+        [--cases C3 C2 C5] [--reps 20] [--series N]
+        [--out profiles/panel_probe.json]
+
+--baseline-lib: the parent commit's build (check the parent out beside the
+tree, build it there, pass its libotsdb_agg.so); without it the singles run
+on this tree's library and the line says so.  Shapes: the per-GPU series
+counts of C3 (1h buckets, {dc=*}), C2 (5m, {host=*}) and C5's shape (1m
+buckets, one group).  Panels: [min-min, avg-avg, max-max] and the same plus
+sum-sum.  After the warm-up rounds the two alternate, each timed
+synchronously; per case the median, min and max of the repetitions, and the
+routing rule of DESIGN.md §4.2: the shared pass stays the default for a
+shape only if its median is below the baseline's by more than the baseline's
+own min-max spread.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+PANELS = [[("min", "min"), ("avg", "avg"), ("max", "max")],
+          [("min", "min"), ("avg", "avg"), ("max", "max"), ("sum", "sum")]]
+
+
+def with_query(spec, agg, ds):
+    from opentsdb_amd import core
+    s = type(spec).from_buffer_copy(spec)
+    s.agg_id = core.Aggregators.get(agg).id
+    s.ds_agg_id = core.Aggregators.get(ds).id
+    s.interp = -1
+    return s
+
+
+class BaselineEngine:
+    """A context of another build of the library (abi.load(path)): only the
+    single device query is called on it."""
+
+    def __init__(self, path):
+        from opentsdb_amd import abi
+        self.lib = abi.load(path)
+        self.ctx = C.c_void_p()
+        st = self.lib.otsdb_ctx_create(0, C.byref(self.ctx))
+        assert st == 0, st
+
+    def run_device(self, spec, b, r):
+        st = self.lib.otsdb_agg_run_device(self.ctx, C.byref(spec),
+                                           C.byref(b), C.byref(r), None)
+        assert st == 0, (st, self.lib.otsdb_last_error())
+
+    def close(self):
+        self.lib.otsdb_ctx_destroy(self.ctx)
+
+
+def probe(eng, base, config, n_series, warm, reps):
+    import torch
+    from opentsdb_amd import workload
+    from opentsdb_amd.engine import DeviceResult, run_panel_device
+    g = workload.gen_spec(config)
+    db = workload.generate_device(eng, g, 0, n_series, config=config)
+    spec = workload.query_spec(config)
+    b_abi = db.as_abi()
+
+    def timed(fn):
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3
+
+    lines = []
+    for queries in PANELS:
+        n = len(queries)
+        sz = eng.plan_panel(spec, queries, db)
+        cap = int(sz.max_out_points)
+        res = [DeviceResult(torch, db.n_groups, cap, "cuda") for _ in queries]
+        ref = [DeviceResult(torch, db.n_groups, cap, "cuda") for _ in queries]
+        ref_abi = [r.as_abi() for r in ref]
+        specs = [with_query(spec, a, d) for a, d in queries]
+
+        def panel():
+            run_panel_device(eng, spec, queries, db, res)
+
+        def singles():
+            for i in range(n):
+                base.run_device(specs[i], b_abi, ref_abi[i])
+        for _ in range(warm):
+            panel()
+            singles()
+        torch.cuda.synchronize()
+        tp, ts = [], []
+        for _ in range(reps):
+            tp.append(timed(panel))
+            ts.append(timed(singles))
+        panel()
+        counters = eng.panel_counters()
+        # the two must agree before their times are compared
+        same = True
+        for i in range(n):
+            k = int(ref[i].offsets[-1].item())
+            same = (same and torch.equal(res[i].offsets, ref[i].offsets) and
+                    torch.equal(res[i].ts[:k], ref[i].ts[:k]))
+        med_p, med_s = statistics.median(tp), statistics.median(ts)
+        spread = max(ts) - min(ts)
+        lines.append(dict(
+            config=config, panel=["%s-%s" % q for q in queries], n_out=n,
+            series=n_series, points=int(db.n_points_total),
+            groups=int(db.n_groups), buckets=int(sz.n_buckets), reps=reps,
+            warmup=warm,
+            panel_ms=dict(median=med_p, min=min(tp), max=max(tp)),
+            singles_ms=dict(median=med_s, min=min(ts), max=max(ts)),
+            baseline=base.path, singles_over_panel=med_s / med_p,
+            counters=counters, same_timestamps=bool(same),
+            shared_pass_stays=bool(med_s - med_p > spread)))
+        print(json.dumps(lines[-1]), flush=True)
+        del res, ref
+    return lines
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", nargs="*", default=["C3", "C2", "C5"])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--series", type=int, default=0,
+                    help="series per case (default: the config's per GPU)")
+    ap.add_argument("--baseline-lib", default=None,
+                    help="libotsdb_agg.so built from the parent commit")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from opentsdb_amd import abi, build, workload
+    from opentsdb_amd.engine import Engine
+    build.build()
+    eng = Engine(0)
+    base = BaselineEngine(a.baseline_lib or abi.LIB_PATH)
+    base.path = ("parent commit" if a.baseline_lib
+                 else "this tree (no --baseline-lib)")
+    lines = []
+    for config in a.cases:
+        n = a.series or workload.default_series_per_gpu(config)
+        lines += probe(eng, base, config, n, a.warmup, max(a.reps, 1))
+        import torch
+        torch.cuda.empty_cache()
+    base.close()
+    eng.close()
+    if a.out:
+        with open(a.out, "w") as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
+
+
+if __name__ == "__main__":
+    main()
