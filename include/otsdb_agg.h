@@ -624,8 +624,35 @@ otsdb_status otsdb_agg_run_cells_multi_device(otsdb_ctx* ctx,
                                               const otsdb_batch* batch,
                                               otsdb_result* outs,
                                               void* hip_stream);
-/* The same with HOST pointers (the JNI entry at the TsdbQuery seam: the
- * Spans' RowSeq bytes, SpanGroup members); copies in, runs, copies the
+/* A panel request from the columns (otsdb_agg_run_panel_device's contract and
+ * argument checks; the routing is otsdb_agg_run_cells_device's): output i is
+ * what otsdb_agg_run_cells_device gives for ds_agg_ids[i] / agg_ids[i] /
+ * interps[i].  Two or more distinct functions of the envelope set are reduced
+ * from ONE decode of each series' columns into one row matrix per function,
+ * bit for bit the rows of the single function's cells pass (DESIGN.md
+ * §4.2.1) — in place of one cells query per function, each decoding the same
+ * ≈10 B / point again, or a caller-side decode to 16 B / point columns before
+ * otsdb_agg_run_panel_device.  A column mixing qualifier widths is rewritten
+ * once and the pass runs again; a corrupt column is OTSDB_E_ILLEGAL_DATA for
+ * every output.  The other functions of such a request run one cells call
+ * each; one distinct function is otsdb_agg_run_cells_multi_device.  What the
+ * fused path does not take ("all" downsampling, rate, per-series calendar
+ * anchors, raw group-by, grids past the row limits) is decoded once into the
+ * context-owned columnar buffer and runs as otsdb_agg_run_panel_device.
+ * Same results either way; otsdb_ctx_counters [10] / [11] as for the columnar
+ * entry (a pass run again after the rewrite counts again).                  */
+otsdb_status otsdb_agg_run_cells_panel_device(otsdb_ctx* ctx,
+                                              const otsdb_query_spec* spec,
+                                              int32_t n_out,
+                                              const int32_t* ds_agg_ids,
+                                              const int32_t* agg_ids,
+                                              const int32_t* interps,
+                                              const otsdb_cells* cells,
+                                              const otsdb_batch* batch,
+                                              otsdb_result* outs,
+                                              void* hip_stream);
+/* otsdb_agg_run_cells_device with HOST pointers (the JNI entry at the
+ * TsdbQuery seam: the Spans' RowSeq bytes, SpanGroup members); copies in, runs, copies the
  * result out.  Synchronous.  row_series must be nondecreasing.            */
 otsdb_status otsdb_agg_run_cells(otsdb_ctx* ctx, const otsdb_query_spec* spec,
                                  const otsdb_cells* cells,

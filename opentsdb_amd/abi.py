@@ -155,7 +155,7 @@ EXPORTS = [
     "otsdb_agg_partials_multi_device", "otsdb_agg_finalize_multi_device",
     "otsdb_sel_retarget",
     "otsdb_agg_plan_panel", "otsdb_agg_run_panel_device",
-    "otsdb_agg_run_panel",
+    "otsdb_agg_run_panel", "otsdb_agg_run_cells_panel_device",
 ]
 
 MULTI_MAX = 32  # OTSDB_MULTI_MAX
@@ -281,6 +281,12 @@ def load(path=None):
         lib.otsdb_agg_run_panel_device.restype = C.c_int
         lib.otsdb_agg_run_panel.argtypes = [vp, PS, i32, vp, vp, vp, PB, PR]
         lib.otsdb_agg_run_panel.restype = C.c_int
+    # the panel call from compacted columns: (ctx, spec, n_out, ds_agg_ids,
+    # agg_ids, interps, cells, batch, results[n_out], stream)
+    if hasattr(lib, "otsdb_agg_run_cells_panel_device"):
+        lib.otsdb_agg_run_cells_panel_device.argtypes = [vp, PS, i32, vp, vp,
+                                                         vp, PC, PB, PR, vp]
+        lib.otsdb_agg_run_cells_panel_device.restype = C.c_int
     # bound only on the ABI it was added to: a stale library of another
     # version must not hand out a symbol of other arguments
     if lib.otsdb_abi_version() == 6 and hasattr(lib, "otsdb_sel_retarget"):

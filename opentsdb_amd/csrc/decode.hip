@@ -657,11 +657,38 @@ __global__ void k_series_rows(int64_t R, int64_t S,
 }
 #endif  // OTSDB_DS_TU
 
-template <class M, int K, int WAVES = 1, int ABL = 0>
+// What k_bucketize_cells' walk is compiled over beside its state M: the row
+// matrices, where closed buckets go (a sink: close(k, state, err)) and what is
+// kept of the bucket past the window.  CellsOne: one downsampler — one matrix,
+// RowSink's direct form with state bytes, the state's finished value in
+// SeriesMeta.of_val.  (The panel walk, panel.hip, keeps the combined state
+// and finishes it once per function.)
+struct CellsOne {
+  using Rows = otsdb::Rows;
+  using Sink = RowSink;
+  using OfVal = double;
+  static constexpr bool kRate = true;  // rate queries: the kept rates beyond
+  DEV static RowSink sink(const Rows& R, int64_t s, int64_t nb) {
+    return RowSink{R.val + s * nb, R.state + s * nb, nullptr, 0, 1, 1, 0, 0};
+  }
+  DEV static double of_zero() { return 0.0; }
+  template <class M>
+  DEV static double of_finish(const M& st) {
+    int e2 = 0;
+    return st.finish(&e2);
+  }
+  DEV static void of_store(const SeriesMeta& SM, const Rows&, int64_t s,
+                           double v) {
+    SM.of_val[s] = v;
+  }
+};
+
+template <class M, int K, int WAVES = 1, int ABL = 0, class X = CellsOne>
 __global__ __launch_bounds__(256, WAVES) void k_bucketize_cells(
     Params P, CellsDev C, const int64_t* __restrict__ series_row, int64_t S,
-    SeriesMeta SM, Rows R, int* err_word) {
+    SeriesMeta SM, typename X::Rows R, int* err_word) {
   static_assert(K % 2 == 0, "K");
+  using OfVal = typename X::OfVal;
   constexpr int PTS = 64 * K;
   constexpr int QB = PTS * 4 + 32, VB = PTS * 8 + 64;
   // two buffers per wave: row r is read from one while row r + 1 lands in
@@ -673,7 +700,7 @@ __global__ __launch_bounds__(256, WAVES) void k_bucketize_cells(
   const int64_t s = (int64_t)blockIdx.x * 4 + wv;
   if (s >= S) return;
   const int64_t r0 = series_row[s], r1 = series_row[s + 1];
-  auto meta = [&](bool keep, uint8_t of_has, int64_t of_ts, double of_val) {
+  auto meta = [&](bool keep, uint8_t of_has, int64_t of_ts, OfVal of_val) {
     if (lane == 0) {
       SM.keep[s] = keep;
       SM.lo[s] = 0;
@@ -682,7 +709,7 @@ __global__ __launch_bounds__(256, WAVES) void k_bucketize_cells(
       SM.kl[s] = -1;
       SM.of_has[s] = of_has;
       SM.of_ts[s] = of_ts;
-      SM.of_val[s] = of_val;
+      X::of_store(SM, R, s, of_val);
     }
   };
   // SpanGroup.add filter (SpanGroup.java:321-338) from the first and last
@@ -692,7 +719,7 @@ __global__ __launch_bounds__(256, WAVES) void k_bucketize_cells(
     const CellRow a = cell_row(C, r0), z = cell_row(C, r1 - 1);
     if (!a.ok || !z.ok) {
       if (lane == 0) atomicOr(err_word, ERR_CELLS_GENERIC);
-      meta(false, 0, 0, 0.0);
+      meta(false, 0, 0, X::of_zero());
       return;
     }
     const int64_t t_first = qual_ts(a.base_ms, a.qw, cell_qual(a, 0));
@@ -700,11 +727,11 @@ __global__ __launch_bounds__(256, WAVES) void k_bucketize_cells(
     keep = t_first <= P.end_ms && t_last >= P.start_ms;
   }
   if (!keep) {
-    meta(false, 0, 0, 0.0);
+    meta(false, 0, 0, X::of_zero());
     return;
   }
   BatchDev Bd{0, nullptr, nullptr, nullptr, nullptr, nullptr};
-  RowSink Sk{R.val + s * P.nb, R.state + s * P.nb, nullptr, 0, 1, 1, 0, 0};
+  typename X::Sink Sk = X::sink(R, s, P.nb);
   int err = 0, carry_key = INT32_MIN;
   M carry = M::init();
   int64_t stop_r = -1, stop_i = 0;  // first point at or past stop_ts
@@ -907,7 +934,7 @@ __global__ __launch_bounds__(256, WAVES) void k_bucketize_cells(
         }
       }
       const int64_t lo = st0 + sum_seek, hi = st0 + sum_stop;
-      if (ABL == 1) {  // tuning ablation: decode only, no reduction
+      if constexpr (ABL == 1) {  // tuning ablation: decode only, no reduction
         int64_t x = 0;
 #pragma unroll
         for (int j = 0; j < K; ++j) x ^= t[j] + v[j];
@@ -943,16 +970,16 @@ __global__ __launch_bounds__(256, WAVES) void k_bucketize_cells(
     // whether it is corrupt
     if (lane == 0)
       atomicOr(err_word, generic ? ERR_CELLS_GENERIC : ERR_CORRUPT_CELL);
-    meta(false, 0, 0, 0.0);
+    meta(false, 0, 0, X::of_zero());
     return;
   }
   if (carry_key >= 0 && carry_key < P.nb && lane == 0)
-    Sk.put(carry_key, carry.finish(&err));
+    Sk.close(carry_key, carry, err);
   // the first bucket past the window (k_prep's of_val): lane 0 folds its
   // points in order, across rows (NONE fill only, like k_prep)
   uint8_t of_has = 0;
   int64_t of_ts = 0;
-  double of_val = 0.0;
+  OfVal of_val = X::of_zero();
   if (!P.run_all && P.fill == 0 && stop_r >= 0 && lane == 0) {
     CellRow w = cell_row(C, stop_r);
     // value offset of point stop_i: the lengths of the points before it
@@ -977,7 +1004,7 @@ __global__ __launch_bounds__(256, WAVES) void k_bucketize_cells(
       int64_t r = stop_r, i = stop_i;
       // folds the points of [.., end) from (r, i) on, across rows; false
       // when the span has no point left
-      auto fold_until = [&](int64_t end, double* out) -> bool {
+      auto fold_until = [&](int64_t end, OfVal* out) -> bool {
         M st = M::init();
         bool any = false;
         while (r < r1) {
@@ -1001,13 +1028,13 @@ __global__ __launch_bounds__(256, WAVES) void k_bucketize_cells(
           ++i;
           any = true;
         }
-        int e2 = 0;
-        *out = st.finish(&e2);
+        *out = X::of_finish(st);
         return any;
       };
       fold_until(e, &of_val);
       of_has = 1;
-      if (P.rate) {  // kept rates past that bucket (k_prep's rates_beyond)
+      // kept rates past that bucket (k_prep's rates_beyond)
+      if constexpr (X::kRate) if (P.rate) {
         auto next = [&](int64_t* tn, double* vn) -> bool {
           if (r >= r1 || i >= w.n) return false;
           const int64_t tt = qual_ts(w.base_ms, w.qw, cell_qual(w, i));

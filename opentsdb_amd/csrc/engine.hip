@@ -2703,6 +2703,82 @@ struct PanelOutcome {
   }
 };
 
+// The envelope functions E of a request as one pass: every function's request,
+// spec and work set, and the outputs in the order the pass compacts them.
+struct PanelPass {
+  std::vector<MultiState> MS;
+  std::vector<otsdb_query_spec> sp;
+  std::vector<MultiReq> qs;
+  std::vector<int> orig;
+  std::vector<otsdb_result> outs;
+  PanelPass(const otsdb_query_spec* spec, const PanelReq& q,
+            std::vector<PanelFunc*>& E)
+      : MS(E.size()), sp(E.size(), *spec), qs(E.size()) {
+    for (size_t d = 0; d < E.size(); ++d) {
+      sp[d].ds_agg_id = E[d]->ds;
+      qs[d] = E[d]->req(q, (int)orig.size());
+      sp[d].agg_id = qs[d].aggs[0];
+      for (size_t j = 0; j < E[d]->idx.size(); ++j) {
+        orig.push_back(E[d]->idx[j]);
+        outs.push_back(E[d]->outs[j]);
+      }
+    }
+  }
+};
+
+// every function's buffers carved from one workspace (multi_build: a sizing
+// pass, ensure, the carving pass), the error words and the counters cleared
+otsdb_status panel_build(otsdb_ctx* c, PanelPass& X, const BatchDev& B,
+                         const int64_t* d_members, std::vector<int64_t>& goff,
+                         const Params& P, const CellsDev* cells) {
+  hipStream_t st = c->stream;
+  const int D = (int)X.MS.size();
+  otsdb_status rc;
+  size_t total = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 1) {
+      rc = ensure(&c->ws, &c->ws_cap, total);
+      if (rc) return rc;
+    }
+    size_t off = 0;
+    for (int d = 0; d < D; ++d) {
+      PanelPart part{off, 0, pass == 0};
+      rc = multi_build(c, &X.sp[d], X.qs[d], B, d_members, goff, P, cells,
+                       nullptr, X.MS[d], false, &part);
+      if (rc) return rc;
+      off += (part.ws_need + 255) & ~(size_t)255;
+    }
+    total = off;
+  }
+  HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(int), st));
+  HIP_TRY(hipMemsetAsync(c->d_merr, 0, OTSDB_MULTI_MAX * sizeof(int), st));
+  c->clean_entry = false;
+  c->n_multi_ds = c->n_multi_group = c->n_multi_kt = c->n_multi_tf = 0;
+  return OTSDB_OK;
+}
+
+// the existing multi_aggregate over each matrix, every output compacted, one
+// synchronisation
+otsdb_status panel_finish(otsdb_ctx* c, PanelPass& X, PanelOutcome& O) {
+  const int D = (int)X.MS.size();
+  otsdb_status rc;
+  for (int d = 0; d < D; ++d) {
+    rc = multi_aggregate(c, X.MS[d], /*compact_now=*/false);
+    if (rc) return rc;
+  }
+  for (int d = 0; d < D; ++d) {
+    rc = multi_compact_launch(c, X.qs[d], X.MS[d].P, X.MS[d].G,
+                              X.MS[d].out_val, X.MS[d].out_emit);
+    if (rc) return rc;
+  }
+  const MultiReq all{(int32_t)X.orig.size(), nullptr, nullptr, X.outs.data()};
+  rc = multi_compact_wait(c, all, X.orig.data());
+  for (size_t j = 0; j < X.orig.size(); ++j)
+    O.total[X.orig[j]] = c->multi_total[X.orig[j]];
+  if (rc) O.fail_at(c, c->multi_failed, rc);
+  return OTSDB_OK;
+}
+
 // The envelope functions E of a request over one pass of the point stream:
 // every function's buffers carved from one workspace (multi_build), prep, the
 // envelope kernel into the D row matrices, the existing multi_aggregate over
@@ -2715,41 +2791,10 @@ otsdb_status panel_shared(otsdb_ctx* c, const otsdb_query_spec* spec,
   const int D = (int)E.size();
   BatchDev B{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
              b->series_float};
-  std::vector<MultiState> MS((size_t)D);
-  std::vector<otsdb_query_spec> sp((size_t)D, *spec);
-  std::vector<MultiReq> qs((size_t)D);
-  std::vector<int> orig;
-  std::vector<otsdb_result> outs;
-  for (int d = 0; d < D; ++d) {
-    sp[d].ds_agg_id = E[d]->ds;
-    qs[d] = E[d]->req(q, (int)orig.size());
-    sp[d].agg_id = qs[d].aggs[0];
-    for (size_t j = 0; j < E[d]->idx.size(); ++j) {
-      orig.push_back(E[d]->idx[j]);
-      outs.push_back(E[d]->outs[j]);
-    }
-  }
-  otsdb_status rc;
-  size_t total = 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass == 1) {
-      rc = ensure(&c->ws, &c->ws_cap, total);
-      if (rc) return rc;
-    }
-    size_t off = 0;
-    for (int d = 0; d < D; ++d) {
-      PanelPart part{off, 0, pass == 0};
-      rc = multi_build(c, &sp[d], qs[d], B, b->group_members, goff, P, nullptr,
-                       nullptr, MS[d], false, &part);
-      if (rc) return rc;
-      off += (part.ws_need + 255) & ~(size_t)255;
-    }
-    total = off;
-  }
-  HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(int), st));
-  HIP_TRY(hipMemsetAsync(c->d_merr, 0, OTSDB_MULTI_MAX * sizeof(int), st));
-  c->clean_entry = false;
-  c->n_multi_ds = c->n_multi_group = c->n_multi_kt = c->n_multi_tf = 0;
+  PanelPass X(spec, q, E);
+  std::vector<MultiState>& MS = X.MS;
+  otsdb_status rc = panel_build(c, X, B, b->group_members, goff, P, nullptr);
+  if (rc) return rc;
   // ---- prep.  Bounds, seek and the first / last bucket do not depend on
   // the function: one launch, shared by every function's work set.  Only
   // under NONE fill k_prep also downsamples the bucket past the window with
@@ -2792,21 +2837,7 @@ otsdb_status panel_shared(otsdb_ctx* c, const otsdb_query_spec* spec,
   ++c->n_multi_ds;
   ++c->n_panel_passes;
   c->n_panel_mats += D;
-  for (int d = 0; d < D; ++d) {
-    rc = multi_aggregate(c, MS[d], /*compact_now=*/false);
-    if (rc) return rc;
-  }
-  for (int d = 0; d < D; ++d) {
-    rc = multi_compact_launch(c, qs[d], MS[d].P, MS[d].G, MS[d].out_val,
-                              MS[d].out_emit);
-    if (rc) return rc;
-  }
-  const MultiReq all{(int32_t)orig.size(), nullptr, nullptr, outs.data()};
-  rc = multi_compact_wait(c, all, orig.data());
-  for (size_t j = 0; j < orig.size(); ++j)
-    O.total[orig[j]] = c->multi_total[orig[j]];
-  if (rc) O.fail_at(c, c->multi_failed, rc);
-  return OTSDB_OK;
+  return panel_finish(c, X, O);
 }
 
 otsdb_status run_panel_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
@@ -3006,6 +3037,9 @@ otsdb_status requal_impl(otsdb_ctx* c, const CellsDev& C, CellsDev* out,
   return OTSDB_OK;
 }
 
+otsdb_status cells_columnar(otsdb_ctx* c, const otsdb_cells* cells,
+                            const otsdb_batch* b, otsdb_batch* cb_out);
+
 // Query straight from compacted columns: the fused decode + downsample when
 // the query and the columns allow it, else decode -> columnar -> pipeline.
 // mq: several aggregators (otsdb_agg_run_cells_multi_device; `spec` carries
@@ -3097,7 +3131,21 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   // decode to a columnar batch in the context's own buffer, then the
   // columnar pipeline (raw group-by, median/percentile or "all" downsampling,
   // mixed-width columns)
-  rc = ensure(&c->cells_ws, &c->cells_ws_cap, (size_t)(S + 1) * 8 + 64);
+  otsdb_batch cb;
+  rc = cells_columnar(c, cells, b, &cb);
+  if (rc) return rc;
+  if (mq) return run_multi_impl(c, spec, *mq, &cb, goff);
+  return run_device_impl(c, spec, &cb, out, goff);
+}
+
+// The compacted columns decoded into the context's own columnar buffer: *cb
+// is b over them (the fallback of the fused cells queries).
+otsdb_status cells_columnar(otsdb_ctx* c, const otsdb_cells* cells,
+                            const otsdb_batch* b, otsdb_batch* cb_out) {
+  hipStream_t st = c->stream;
+  const int64_t S = b->n_series;
+  otsdb_status rc =
+      ensure(&c->cells_ws, &c->cells_ws_cap, (size_t)(S + 1) * 8 + 64);
   if (rc) return rc;
   int64_t* offs = (int64_t*)c->cells_ws;
   // the generic decode (its own stage; released before the pipeline)
@@ -3124,8 +3172,188 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   cb.val = vv;
   cb.is_float = isf;
   cb.series_float = nullptr;
-  if (mq) return run_multi_impl(c, spec, *mq, &cb, goff);
-  return run_device_impl(c, spec, &cb, out, goff);
+  *cb_out = cb;
+  return OTSDB_OK;
+}
+
+// One attempt of the shared cells pass: the functions' buffers, the state
+// matrices cleared (multi_build, sentinel = 0), k_bucketize_panel_cells once
+// into the D matrices.  The caller reads the error word before it aggregates.
+otsdb_status cells_panel_rows(otsdb_ctx* c, PanelPass& X,
+                              std::vector<PanelFunc*>& E, const BatchDev& B,
+                              const int64_t* d_members,
+                              std::vector<int64_t>& goff, const Params& P,
+                              const CellsDev& C, const int64_t* series_row) {
+  const int D = (int)E.size();
+  std::vector<MultiState>& MS = X.MS;
+  otsdb_status rc = panel_build(c, X, B, d_members, goff, P, &C);
+  if (rc) return rc;
+  // keep, lo, hi, kf, kl, of_has and of_ts do not depend on the function:
+  // one set of arrays; every function its own of_val (NONE fill: what its
+  // rows interpolate toward)
+  PanelCellsRows R{};
+  for (int d = 0; d < D; ++d) {
+    Work& W = MS[d].W;
+    double* const ov = W.SM.of_val;
+    W.SM = MS[0].W.SM;
+    W.SM.of_val = ov;
+    switch (E[d]->fn) {
+      case PF_SUM: R.sum = W.R.val, R.st_sum = W.R.state, R.of_sum = ov; break;
+      case PF_AVG: R.avg = W.R.val, R.st_avg = W.R.state, R.of_avg = ov; break;
+      case PF_CNT: R.cnt = W.R.val, R.st_cnt = W.R.state, R.of_cnt = ov; break;
+      case PF_MIN: R.min = W.R.val, R.st_min = W.R.state, R.of_min = ov; break;
+      default: R.max = W.R.val, R.st_max = W.R.state, R.of_max = ov; break;
+    }
+    R.fn |= E[d]->fn;
+  }
+  {
+    StageTimer tm(c, 0);
+    launch_panel_cells(c->stream, MS[0].P, C, series_row, B.S, MS[0].W.SM, R,
+                       c->d_err);
+  }
+  HIP_TRY(hipGetLastError());
+  ++c->n_multi_ds;
+  ++c->n_panel_passes;  // (one per attempt; the matrices are the last one's)
+  c->n_panel_mats = D;
+  return OTSDB_OK;
+}
+
+// otsdb_agg_run_cells_panel_device: run_cells_impl's routing for a panel
+// request.  Two or more envelope functions of a query the fused cells path
+// takes share one pass over the compacted columns (the decode runs once for
+// all of them), inside run_cells_impl's attempt loop: a column of mixed
+// qualifier widths is rewritten once and the pass runs again, a corrupt one
+// fails every output.  The other functions of such a request then run one
+// cells call each.  One distinct function is the cells multi call.  What the
+// fused path does not take (`all`, anchored calendars, rate, raw group-by,
+// grids past the limits, columns still generic after the rewrite) is decoded
+// once into the context's columnar buffer and runs as the columnar panel
+// call.
+otsdb_status run_cells_panel_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
+                                  const PanelReq& q, const otsdb_cells* cells,
+                                  const otsdb_batch* b,
+                                  std::vector<int64_t>& goff) {
+  hipStream_t st = c->stream;
+  const int64_t S = b->n_series, R = cells->n_rows;
+  if (S < 0 || R < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
+  c->multi_failed = -1;
+  c->n_panel_passes = c->n_panel_mats = 0;
+  std::vector<PanelFunc> F = panel_funcs(spec, q);
+  PanelOutcome O;
+  // one cells call for function f's outputs (the single query for one)
+  auto run_func = [&](PanelFunc& f) {
+    otsdb_query_spec sf = *spec;
+    sf.ds_agg_id = f.ds;
+    const MultiReq mq = f.req(q, 0);
+    sf.agg_id = mq.aggs[0];
+    sf.interp = mq.interps ? mq.interps[0] : OTSDB_INTERP_DEFAULT;
+    c->result_short = false;
+    c->multi_failed = -1;
+    otsdb_status rc;
+    if (mq.n == 1) {
+      c->n_multi_ds = c->n_multi_group = 1;
+      c->n_multi_kt = c->n_multi_tf = 0;
+      rc = run_cells_impl(c, &sf, cells, b, &mq.outs[0], goff);
+      if (!rc) c->multi_total[0] = c->h_small[1];
+    } else {
+      rc = run_cells_impl(c, &sf, cells, b, nullptr, goff, &mq);
+    }
+    c->n_panel_passes += c->n_multi_ds;
+    c->n_panel_mats += c->n_multi_ds;
+    if (rc) {
+      const int j = c->multi_failed >= 0 ? c->multi_failed : 0;
+      O.fail_at(c, f.idx[(size_t)j], rc);
+      return;
+    }
+    for (size_t j = 0; j < f.idx.size(); ++j)
+      O.total[f.idx[j]] = c->multi_total[j];
+  };
+  auto outcome = [&]() -> otsdb_status {
+    for (int i = 0; i < q.n; ++i) c->multi_total[i] = O.total[i];
+    if (O.failed < 0) return OTSDB_OK;
+    c->multi_failed = O.failed;
+    c->result_short = O.result_short;
+    g_last_error = O.msg;
+    return O.rc;
+  };
+  std::vector<PanelFunc*> E;
+  for (PanelFunc& f : F)
+    if (f.fn) E.push_back(&f);
+  const bool ds = spec->ds_interval_ms > 0 || spec->run_all;
+  bool shared = ds && E.size() >= 2 && !spec->rate && !spec->run_all &&
+                !anchored(spec);
+  Params P;
+  if (shared) {
+    const otsdb_query_spec s0 = panel_spec(spec, q, E[0]->idx[0]);
+    shared = make_params(&s0, &P, c) == OTSDB_OK && !P.ds_sel && !P.run_all;
+  }
+  for (size_t d = 0; shared && d < E.size(); ++d) {
+    otsdb_query_spec sd = *spec;
+    sd.ds_agg_id = E[d]->ds;
+    shared = multi_shares_rows(&sd, E[d]->req(q, 0), P, S, goff, 1,
+                               (int)E.size());
+  }
+  if (shared) {
+    otsdb_status rc = ensure(&c->cells_ws, &c->cells_ws_cap, (size_t)(S + 1) * 8);
+    if (rc) return rc;
+    int64_t* series_row = (int64_t*)c->cells_ws;
+    hipLaunchKernelGGL(k_series_rows, dim3(blocks_for(R + 1, 256)), dim3(256),
+                       0, st, R, S, cells->row_series, series_row);
+    BatchDev B{S, nullptr, nullptr, nullptr, nullptr, nullptr};
+    P.check_order = c->verbatim ? 1 : 0;
+    const CellsDev C{R, cells->row_series, cells->row_base_s, cells->qual_off,
+                     cells->qual, cells->val_off, cells->val};
+    CellsDev CQ = C;
+    PanelPass X(spec, q, E);
+    bool requaled = false, done = false;
+    // run_cells_impl's attempts (the row kernel raises no ERR_CELLS_NONUNI:
+    // at most the pass, the rewrite, the pass again)
+    for (int attempt = 0; attempt < 4 && !done; ++attempt) {
+      rc = cells_panel_rows(c, X, E, B, b->group_members, goff, P, CQ,
+                            series_row);
+      if (rc) return rc;
+      HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
+                             hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      const int e = (int)(c->h_small[0] & 0xFFFFFFFF);
+      if (e & ERR_CELLS_NONUNI) continue;
+      if (c->verbatim && (e & (ERR_CORRUPT_CELL | ERR_CELLS_GENERIC |
+                               ERR_NOT_SORTED | ERR_SPEC_MISS)))
+        return spec_miss(c);
+      if (e & ERR_CORRUPT_CELL) {
+        // the columns are every output's: all fail, the lowest index reports
+        c->multi_failed = 0;
+        return fail(OTSDB_E_ILLEGAL_DATA,
+                    "Corrupted value: couldn't break down into individual values");
+      }
+      if (!(e & ERR_CELLS_GENERIC)) {
+        rc = panel_finish(c, X, O);
+        if (rc) return rc;
+        done = true;
+        break;
+      }
+      if (requaled) break;
+      requaled = true;
+      std::unique_ptr<StageTimer> rq_tm(new StageTimer(c, 7));
+      rc = requal_impl(c, C, &CQ, st);
+      if (rc) return rc;
+    }
+    if (done) {
+      for (PanelFunc& f : F)
+        if (!f.fn) run_func(f);
+      return outcome();
+    }
+    if (c->verbatim) return spec_miss(c);
+    c->n_panel_passes = c->n_panel_mats = 0;
+  } else if (F.size() == 1) {
+    run_func(F[0]);
+    return outcome();
+  }
+  // one decode for the whole panel, then the columnar panel call
+  otsdb_batch cb;
+  const otsdb_status rc = cells_columnar(c, cells, b, &cb);
+  if (rc) return rc;
+  return run_panel_impl(c, spec, q, &cb, goff);
 }
 
 // ----------------------------------------- storage rows -> compacted rows
@@ -4008,6 +4236,25 @@ otsdb_status otsdb_agg_run_cells_multi_device(
     return run_cells_impl(c, &s0, cells, b, &outs[0], goff);
   }
   return run_cells_impl(c, &s0, cells, b, nullptr, goff, &q);
+}
+
+otsdb_status otsdb_agg_run_cells_panel_device(
+    otsdb_ctx* c, const otsdb_query_spec* spec, int32_t n_out,
+    const int32_t* ds_agg_ids, const int32_t* agg_ids, const int32_t* interps,
+    const otsdb_cells* cells, const otsdb_batch* b, otsdb_result* outs,
+    void* hip_stream) {
+  if (!c || !spec || !cells || !b || !outs)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  const PanelReq q{n_out, ds_agg_ids, agg_ids, interps, outs};
+  otsdb_status rc = check_panel(spec, q);
+  if (rc) return rc;
+  CtxLock lk(c);
+  HIP_TRY(hipSetDevice(c->device));
+  StreamBinding bind(c, hip_stream);
+  std::vector<int64_t> goff;
+  rc = read_goff(c, b, true, goff);
+  if (rc) return rc;
+  return run_cells_panel_impl(c, spec, q, cells, b, goff);
 }
 
 }  // extern "C"

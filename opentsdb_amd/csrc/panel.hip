@@ -10,7 +10,9 @@
 // count, min, max), each through its own per-wavefront LDS ring.  Every
 // component of MEnv is MSum<0|1|3> / MMinMax<false|true> operation for
 // operation, in the same order, so row i is bit for bit the row
-// k_bucketize_k<M_i> writes.  (Included by engine.hip after kernels.hip.)
+// k_bucketize_k<M_i> writes.  The same from compacted cells, below:
+// k_bucketize_panel_cells, k_bucketize_cells' walk over MEnv (DESIGN.md
+// §4.2.1).  (Included by engine.hip after kernels.hip and decode.hip.)
 #ifndef OTSDB_RING_WIN
 #define OTSDB_RING_WIN 256
 #endif
@@ -190,6 +192,91 @@ inline void launch_panel(hipStream_t st, const Params& P, const BatchDev& B,
   hipLaunchKernelGGL((k_bucketize_panel<OTSDB_RING_WIN, OTSDB_RING_FL>),
                      dim3((unsigned)((B.S + 3) / 4)), dim3(256),
                      (unsigned)panel_lds_bytes(R.fn), st, P, B, SM, R);
+}
+
+// ------------------------------------------------ the panel pass from cells
+// k_bucketize_panel_cells is k_bucketize_cells (decode.hip: one wavefront per
+// series, row metadata 64 rows at a time, the LDS-DMA double buffers, the
+// uniform and mixed value-length decode, the seek / stop counting, the
+// corrupt / generic flags) instantiated over MEnv and PanelCells: the
+// compacted bytes are read and decoded once for every function of the mask.
+// The cells row path writes rows directly, value plus state byte
+// (Params.sentinel = 0), so the sink is a direct one; the decode and the
+// lanes' summation tree are the single kernel's, so row i is bit for bit the
+// row k_bucketize_cells<M_i> writes.  (engine.hip includes decode.hip first.)
+#ifndef OTSDB_PANEL_CELLS_K    // points a lane per step (even; the static LDS
+#define OTSDB_PANEL_CELLS_K 6  // scales with it): k_bucketize_cells' own
+#endif
+
+// the matrices of one panel pass from cells: value and state rows [S * nb]
+// and the per-series value of the bucket past the window [S], per function
+// (null where fn has no bit)
+struct PanelCellsRows {
+  double *sum, *avg, *cnt, *min, *max;
+  uint8_t *st_sum, *st_avg, *st_cnt, *st_min, *st_max;
+  double *of_sum, *of_avg, *of_cnt, *of_min, *of_max;
+  uint32_t fn;
+};
+
+// RowSink's direct form with state bytes (states = 1) for up to five rows
+struct PanelCellsSink {
+  double *row_sum, *row_avg, *row_cnt, *row_min, *row_max;
+  uint8_t *st_sum, *st_avg, *st_cnt, *st_min, *st_max;
+  uint32_t fn;  // kernel-uniform
+  DEV static void put1(double* rowv, uint8_t* rows, int k, double v) {
+    rowv[k] = v;
+    rows[k] = ST_REAL;
+  }
+  DEV void close(int k, const MEnv& m, int& err) {
+    if (fn & PF_SUM) put1(row_sum, st_sum, k, m.sum());
+    if (fn & PF_AVG) put1(row_avg, st_avg, k, m.avg());
+    if (fn & PF_CNT) put1(row_cnt, st_cnt, k, m.count());
+    if (fn & PF_MIN) put1(row_min, st_min, k, m.min());
+    if (fn & PF_MAX) put1(row_max, st_max, k, m.max());
+  }
+};
+
+// CellsOne's counterpart: the five-row sink, and the bucket past the window
+// kept as its envelope and finished into every function's own of_val (what
+// that function's rows interpolate toward); SeriesMeta's other arrays (keep,
+// lo, hi, kf, kl, of_has, of_ts) do not depend on the function and are shared
+struct PanelCells {
+  using Rows = PanelCellsRows;
+  using Sink = PanelCellsSink;
+  using OfVal = MEnv;
+  static constexpr bool kRate = false;  // (rate queries take no shared pass)
+  DEV static PanelCellsSink sink(const Rows& R, int64_t s, int64_t nb) {
+    const int64_t row = s * nb;
+    return PanelCellsSink{R.sum + row,    R.avg + row,    R.cnt + row,
+                          R.min + row,    R.max + row,    R.st_sum + row,
+                          R.st_avg + row, R.st_cnt + row, R.st_min + row,
+                          R.st_max + row, R.fn};
+  }
+  DEV static MEnv of_zero() { return MEnv::init(); }
+  DEV static MEnv of_finish(const MEnv& st) { return st; }
+  DEV static void of_store(const SeriesMeta&, const Rows& R, int64_t s,
+                           const MEnv& m) {
+    if (R.fn & PF_SUM) R.of_sum[s] = m.sum();
+    if (R.fn & PF_AVG) R.of_avg[s] = m.avg();
+    if (R.fn & PF_CNT) R.of_cnt[s] = m.count();
+    if (R.fn & PF_MIN) R.of_min[s] = m.min();
+    if (R.fn & PF_MAX) R.of_max[s] = m.max();
+  }
+};
+
+// (Params, CellsDev, series_row, S, SeriesMeta, PanelCellsRows, err_word)
+template <int K>
+constexpr auto k_bucketize_panel_cells =
+    &k_bucketize_cells<MEnv, K, 1, 0, PanelCells>;
+
+inline void launch_panel_cells(hipStream_t st, const Params& P,
+                               const CellsDev& C, const int64_t* series_row,
+                               int64_t S, const SeriesMeta& SM,
+                               const PanelCellsRows& R, int* err_word) {
+  if (S <= 0 || !R.fn) return;
+  hipLaunchKernelGGL(k_bucketize_panel_cells<OTSDB_PANEL_CELLS_K>,
+                     dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, P, C,
+                     series_row, S, SM, R, err_word);
 }
 
 }  // namespace otsdb

@@ -287,3 +287,32 @@ def run_cells_multi_device(engine, spec, aggs, cells, db_groups, results,
     engine._check(engine.lib.otsdb_agg_run_cells_multi_device(
         engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
         C.byref(c), C.byref(b), rs, None))
+
+
+def run_cells_panel_device(engine, spec, queries, dcells, dbatch, dresults,
+                           stream=None):
+    """otsdb_agg_run_cells_panel_device: a panel request straight from the
+    compacted columns; dresults[i] takes what run_cells_device gives for
+    queries[i] = (aggregator, downsampling function[, interpolation]).  The
+    envelope functions share one decode + downsample of the columns.
+    dbatch: a DeviceBatch-like object supplying the group arrays."""
+    import ctypes as C
+    from .engine import panel_args
+    n, ds, ids, it = panel_args(queries)
+    if len(dresults) != n:
+        raise core.IllegalArgumentException(
+            "%d results for %d queries" % (len(dresults), n))
+    b = abi.Batch()
+    b.n_series = dcells.n_series
+    b.n_points = 0
+    b.n_groups = dbatch.n_groups
+    b.group_offsets = dbatch.group_offsets.data_ptr()
+    b.group_members = dbatch.group_members.data_ptr()
+    c = dcells.as_abi()
+    rs = (abi.Result * n)()
+    for i, r in enumerate(dresults):
+        rs[i] = r.as_abi()
+    engine._check(engine.lib.otsdb_agg_run_cells_panel_device(
+        engine.ctx, C.byref(spec), n, ds.ctypes.data, ids.ctypes.data,
+        it.ctypes.data, C.byref(c), C.byref(b), rs,
+        None if stream is None else C.c_void_p(stream)))
