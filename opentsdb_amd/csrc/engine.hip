@@ -203,6 +203,33 @@ struct Work {
   bool sel_fused = false;      // fill-mode selection: keys + counts by the transpose
 };
 
+// The blocks run_pipeline's and multi_build's carves have in common, each in
+// the one order of takes both rely on.
+void carve_series(Carve& cv, Work& W, int64_t S) {
+  W.SM.lo = cv.take<int64_t>(S);
+  W.SM.hi = cv.take<int64_t>(S);
+  W.SM.of_ts = cv.take<int64_t>(S);
+  W.SM.of_val = cv.take<double>(S);
+  W.SM.of_rate = cv.take<double>(S);
+  W.SM.kf = cv.take<int32_t>(S);
+  W.SM.kl = cv.take<int32_t>(S);
+  W.SM.keep = cv.take<uint8_t>(S);
+  W.SM.of_has = cv.take<uint8_t>(S);
+  W.redo = cv.take<uint8_t>(S);
+}
+
+// members: all groups' (goff.back()); LG: the large groups; xsel: mode 2
+void carve_selection(Carve& cv, Work& W, int64_t members, int64_t LG,
+                     int64_t NB, bool xsel) {
+  const size_t kt = (size_t)((members + KT_M - 1) / KT_M) * NB;
+  W.keys = cv.take<uint64_t>((size_t)members * NB);
+  W.key_mm = cv.take<uint64_t>(kt * 2);
+  W.key_cnt = cv.take<uint32_t>(kt);
+  W.lg_kept = cv.take<uint32_t>((size_t)LG + 1);
+  W.sel = cv.take<SelState>((size_t)LG * NB);
+  if (xsel) W.xsel = cv.take<XSel>((size_t)LG * NB);
+}
+
 }  // namespace
 
 struct otsdb_ctx {
@@ -364,6 +391,39 @@ struct StreamBinding {
   }
   ~StreamBinding() { c->stream = saved; }
 };
+
+// the context's error word after everything queued on its stream
+otsdb_status read_err(otsdb_ctx* c, int* e) {
+  HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *e = (int)(c->h_small[0] & 0xFFFFFFFF);
+  return OTSDB_OK;
+}
+
+// ERR_RATE_TS as the entries that leave partials report it
+otsdb_status rate_ts_error() {
+  return fail(OTSDB_E_ILLEGAL_STATE,
+              "Next timestamp is supposed to be strictly greater");
+}
+
+BatchDev batch_dev(const otsdb_batch* b) {
+  return BatchDev{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
+                  b->series_float};
+}
+
+// ts_ms / val off the 16-byte alignment of the streaming loads
+bool misaligned(const otsdb_batch* b) {
+  return ((((uintptr_t)b->ts_ms) | ((uintptr_t)b->val)) & 15) != 0;
+}
+
+// what a multi-aggregator call counts: downsample and group passes (0, 0:
+// the reset), no key transpose or class transform yet
+void multi_counters(otsdb_ctx* c, int64_t ds, int64_t group) {
+  c->n_multi_ds = ds;
+  c->n_multi_group = group;
+  c->n_multi_kt = c->n_multi_tf = 0;
+}
 
 // --------------------------------------------------------------- planning
 struct Plan {
@@ -780,6 +840,18 @@ Tiles tiles_of(otsdb_ctx* c, int64_t G) {
 // cut it to ~max_chunks / kCombineSlices
 constexpr int64_t kCombineL1 = 128;
 constexpr int64_t kCombineSlices = 64;
+
+// whether n groups of up to max_chunks tiles combine in two levels (the
+// first-level slices within the budget), and the slices' buffers
+bool two_level_combine(int64_t max_chunks, int64_t n, int64_t NB) {
+  return max_chunks > kCombineL1 &&
+         (double)n * kCombineSlices * NB * 33.0 < 2.0e9;
+}
+
+void carve_combine(Carve& cv, Work& W, int64_t n_comb, int64_t NB) {
+  W.comb = cv.take<Packed>((size_t)n_comb * kCombineSlices * NB);
+  W.comb_emit = cv.take<uint8_t>((size_t)n_comb * kCombineSlices * NB);
+}
 
 // Brackets a pipeline stage with HIP events when profiling is enabled.
 struct StageTimer {
@@ -1215,8 +1287,7 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
   // workspace
   const bool sel_large = is_selection(spec->agg_id) && (T.LG > 0 || mode == 2);
   const int64_t n_comb = (mode == 1) ? G : T.MG;
-  const bool two_level = T.max_chunks > kCombineL1 &&
-                         (double)n_comb * kCombineSlices * NB * 33.0 < 2.0e9;
+  const bool two_level = two_level_combine(T.max_chunks, n_comb, NB);
   const size_t rows = fold ? 0 : (size_t)S * NB;
   WinCtx* wc = nullptr;
   CellsFold CF{};
@@ -1227,16 +1298,7 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
   }
   auto carve = [&](char* base) {
     Carve cv{base};
-    W.SM.lo = cv.take<int64_t>(S);
-    W.SM.hi = cv.take<int64_t>(S);
-    W.SM.of_ts = cv.take<int64_t>(S);
-    W.SM.of_val = cv.take<double>(S);
-    W.SM.of_rate = cv.take<double>(S);
-    W.SM.kf = cv.take<int32_t>(S);
-    W.SM.kl = cv.take<int32_t>(S);
-    W.SM.keep = cv.take<uint8_t>(S);
-    W.SM.of_has = cv.take<uint8_t>(S);
-    W.redo = cv.take<uint8_t>(S);
+    carve_series(cv, W, S);
     W.R.val = cv.take<double>(rows);
     W.R.state = cv.take<uint8_t>(rows);
     W.partial = cv.take<Packed>((size_t)T.T * NB);
@@ -1257,18 +1319,8 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
         CF.wvl0 = cv.take<uint8_t>((size_t)S * (NW - 1));
       }
     }
-    if (two_level) {
-      W.comb = cv.take<Packed>((size_t)n_comb * kCombineSlices * NB);
-      W.comb_emit = cv.take<uint8_t>((size_t)n_comb * kCombineSlices * NB);
-    }
-    if (sel_large) {
-      W.keys = cv.take<uint64_t>((size_t)goff.back() * NB);
-      W.key_mm = cv.take<uint64_t>((size_t)((goff.back() + KT_M - 1) / KT_M) * NB * 2);
-      W.key_cnt = cv.take<uint32_t>((size_t)((goff.back() + KT_M - 1) / KT_M) * NB);
-      W.lg_kept = cv.take<uint32_t>((size_t)T.LG + 1);
-      W.sel = cv.take<SelState>((size_t)T.LG * NB);
-      if (mode == 2) W.xsel = cv.take<XSel>((size_t)T.LG * NB);
-    }
+    if (two_level) carve_combine(cv, W, n_comb, NB);
+    if (sel_large) carve_selection(cv, W, goff.back(), T.LG, NB, mode == 2);
     return cv.off + 256;
   };
   const size_t need = carve(nullptr);
@@ -1614,6 +1666,24 @@ otsdb_status read_goff(otsdb_ctx* c, const otsdb_batch* b, bool device,
   return OTSDB_OK;
 }
 
+// A device entry's scope: the context locked, its device selected, the
+// caller's stream bound and the group offsets read (from the caller's host
+// copy where the batch has one), in that order.  rc: the first failure.
+struct DeviceCall {
+  CtxLock lk;
+  otsdb_status rc;
+  StreamBinding bind;
+  std::vector<int64_t> goff;
+  DeviceCall(otsdb_ctx* c, const otsdb_batch* b, void* hip_stream)
+      : lk(c), rc(select_device(c)), bind(c, hip_stream) {
+    if (!rc) rc = read_goff(c, b, true, goff);
+  }
+  static otsdb_status select_device(otsdb_ctx* c) {
+    HIP_TRY(hipSetDevice(c->device));
+    return OTSDB_OK;
+  }
+};
+
 // Raw (non-downsampled) group-by, raw.hip.  Device pointers throughout.
 otsdb_status run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
                      const otsdb_batch* b, const BatchDev& B,
@@ -1824,7 +1894,7 @@ otsdb_status run_anchored_fill(otsdb_ctx* c, const AnchoredPlan& A,
   uint8_t* isf2 = b->is_float ? (uint8_t*)q[6] : nullptr;
   HIP_TRY(hipMemcpyAsync(fd, A.FD.data(), 8 * nfd, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(cnt + S, 0, 8, st));
-  BatchDev B{S, b->offsets, b->ts_ms, b->val, b->is_float, b->series_float};
+  const BatchDev B = batch_dev(b);
   if (S > 0) {
     hipLaunchKernelGGL(k_cal_fill_count, dim3(blocks_for(S, 4)), dim3(256), 0,
                        st, spec->start_ms, spec->end_ms, B, AC,
@@ -1836,10 +1906,9 @@ otsdb_status run_anchored_fill(otsdb_ctx* c, const AnchoredPlan& A,
                        st, spec->start_ms, A.t_end, B, (const int64_t*)vts, on,
                        (const int64_t*)offs, ts2, val2, isf2);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
-                           hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c->h_small[0] & ERR_CAL_RANGE)
+    int e;
+    if ((rc = read_err(c, &e))) return rc;
+    if (e & ERR_CAL_RANGE)
       return fail(OTSDB_E_UNSUPPORTED,
                   "a point lies before its series' calendar chain");
   }
@@ -1898,7 +1967,7 @@ otsdb_status run_anchored(otsdb_ctx* c, const otsdb_query_spec* spec,
   HIP_TRY(hipMemsetAsync(c->d_err, 0, sizeof(int), st));
   AnchoredCal AC{(const int64_t*)pp[0], (const int64_t*)pp[1],
                  (const int64_t*)pp[2], (const int64_t*)pp[3], na};
-  BatchDev B{S, b->offsets, b->ts_ms, b->val, b->is_float, b->series_float};
+  const BatchDev B = batch_dev(b);
   int64_t* vts = (int64_t*)pp[7];
   if (S > 0) {
     hipLaunchKernelGGL(k_cal_anchor, dim3(blocks_for(S, 256)), dim3(256), 0,
@@ -1911,10 +1980,9 @@ otsdb_status run_anchored(otsdb_ctx* c, const otsdb_query_spec* spec,
                          (const int64_t*)pp[4], (const int64_t*)pp[5],
                          (const int64_t*)pp[6], vts, c->d_err);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
-                           hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c->h_small[0] & ERR_CAL_RANGE)
+    int e;
+    if ((rc = read_err(c, &e))) return rc;
+    if (e & ERR_CAL_RANGE)
       return fail(OTSDB_E_UNSUPPORTED,
                   "a point lies outside its series' calendar chain");
   }
@@ -1933,11 +2001,10 @@ otsdb_status run_device_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   Params P;
   rc = make_params(spec, &P, c);
   if (rc) return rc;
-  if ((((uintptr_t)b->ts_ms) | ((uintptr_t)b->val)) & 15)
+  if (misaligned(b))
     return fail(OTSDB_E_ILLEGAL_ARGUMENT,
                 "ts_ms/val must be 16-byte aligned (16-B streaming loads)");
-  BatchDev B{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
-             b->series_float};
+  const BatchDev B = batch_dev(b);
   if (!(spec->ds_interval_ms > 0 || spec->run_all))
     return run_raw(c, spec, b, B, goff, P, out);
   Work W;
@@ -1950,11 +2017,14 @@ otsdb_status run_device_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   return finish(c, G, out);
 }
 
-// ------------------------------------------------ multi-aggregator queries
+// ----------------------------------- multi-aggregator and panel queries
 // otsdb_agg_run_multi*: n outputs that differ in the cross-series aggregator
 // (and its interpolation) over one query.  DESIGN.md §4.
-struct MultiReq {
+// otsdb_agg_run_panel*: they differ in the downsampling function as well
+// (ds set).  DESIGN.md §4.2.
+struct Req {
   int32_t n;
+  const int32_t* ds;  // null: every output downsamples with spec->ds_agg_id
   const int32_t* aggs;
   const int32_t* interps;  // null: every output its aggregator's own
   otsdb_result* outs;
@@ -1963,21 +2033,30 @@ struct MultiReq {
   int32_t e0 = 0;
 };
 
-otsdb_query_spec multi_spec(const otsdb_query_spec* s, const MultiReq& q,
-                            int i) {
+otsdb_query_spec req_spec(const otsdb_query_spec* s, const Req& q, int i) {
   otsdb_query_spec r = *s;
+  if (q.ds) r.ds_agg_id = q.ds[i];
   r.agg_id = q.aggs[i];
   r.interp = q.interps ? q.interps[i] : OTSDB_INTERP_DEFAULT;
   return r;
 }
 
-otsdb_status check_multi(const otsdb_query_spec* spec, const MultiReq& q) {
+// panel: the entry takes downsampling functions (a null q.ds is its error)
+otsdb_status check_req(const otsdb_query_spec* spec, const Req& q,
+                       bool panel = false) {
   if (q.n < 1 || q.n > OTSDB_MULTI_MAX)
     return fail(OTSDB_E_ILLEGAL_ARGUMENT, "n_out %d outside [1, %d]", (int)q.n,
                 OTSDB_MULTI_MAX);
+  if (panel && (!q.ds || !q.aggs))
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null ds_agg_ids / agg_ids");
   if (!q.aggs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null agg_ids");
+  const bool ds = spec->ds_interval_ms > 0 || spec->run_all;
   for (int i = 0; i < q.n; ++i) {
-    const otsdb_query_spec si = multi_spec(spec, q, i);
+    // (raw group-by has no downsampler: the functions are ignored)
+    if (q.ds && ds && (q.ds[i] < 0 || q.ds[i] >= OTSDB_AGG_COUNT_IDS))
+      return fail(OTSDB_E_NO_SUCH_ELEMENT, "No such downsampling function: %d",
+                  q.ds[i]);
+    const otsdb_query_spec si = req_spec(spec, q, i);
     const otsdb_status rc = check_spec(&si);
     if (rc) return rc;
   }
@@ -1997,7 +2076,7 @@ int multi_kind(int agg) {
 // the rows only for NONE fill without rate (its interpolation branch); the
 // fill branch and transform_rate never read it, so such queries have one
 // class.  cls[i]: class of output i; interp[k]: class k's interpolation.
-int multi_classes(const MultiReq& q, const Params& P, int* cls, int* interp) {
+int multi_classes(const Req& q, const Params& P, int* cls, int* interp) {
   const bool baked = !(P.fill != 0 && !P.run_all) && !P.rate;
   int n = 0;
   for (int i = 0; i < q.n; ++i) {
@@ -2020,7 +2099,7 @@ int multi_classes(const MultiReq& q, const Params& P, int* cls, int* interp) {
 // A panel call asks per downsampling function (panel_shared): a function may
 // have one output (min_n = 1), and the cell and row budgets hold for the
 // `mats` row matrices of the call together.
-bool multi_shares_rows(const otsdb_query_spec* spec, const MultiReq& q,
+bool multi_shares_rows(const otsdb_query_spec* spec, const Req& q,
                        const Params& P, int64_t S,
                        const std::vector<int64_t>& goff, int min_n = 2,
                        int mats = 1) {
@@ -2048,7 +2127,7 @@ bool multi_shares_rows(const otsdb_query_spec* spec, const MultiReq& q,
 
 struct MultiState {
   const otsdb_query_spec* spec;
-  MultiReq q;
+  Req q;
   BatchDev B;
   const int64_t* d_members;
   std::vector<int64_t>* goff;
@@ -2097,7 +2176,7 @@ otsdb_status multi_buffers(otsdb_ctx* c) {
 // the merge across ranks (multi_partials) — dev's chains are those of the
 // single partials entry (kOrderedChunkMerged), its merge covers every group.
 otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
-                         const MultiReq& q, const BatchDev& B,
+                         const Req& q, const BatchDev& B,
                          const int64_t* d_members, std::vector<int64_t>& goff,
                          const Params& P0, const CellsDev* cells,
                          const int64_t* series_row, MultiState& M,
@@ -2142,8 +2221,7 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
   const Tiles T = tiles_of(c, G);
   M.sel_fused = all_sel && sel_fused_path(q.aggs[0], 0, P, T, G);
   const bool sel_large = any_sel && T.LG > 0;
-  M.two_level = T.max_chunks > kCombineL1 &&
-                (double)T.MG * kCombineSlices * NB * 33.0 < 2.0e9;
+  M.two_level = two_level_combine(T.max_chunks, T.MG, NB);
   // dev's own tiles (one chain per group up to kOrderedChunk members): how
   // many groups its merge covers, and its longest
   int64_t mg_dev = 0, max_dev = 0;
@@ -2159,24 +2237,14 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
     }
   }
   if (partial) mg_dev = G;  // k_combine packs every group's state
-  M.two_level_dev = max_dev > kCombineL1 &&
-                    (double)mg_dev * kCombineSlices * NB * 33.0 < 2.0e9;
+  M.two_level_dev = two_level_combine(max_dev, mg_dev, NB);
   const int64_t n_comb = std::max(M.two_level ? T.MG : 0,
                                   M.two_level_dev ? mg_dev : 0);
   const size_t rows = (size_t)S * NB;
   Work& W = M.W;
   auto carve = [&](char* base) {
     Carve cv{base};
-    W.SM.lo = cv.take<int64_t>(S);
-    W.SM.hi = cv.take<int64_t>(S);
-    W.SM.of_ts = cv.take<int64_t>(S);
-    W.SM.of_val = cv.take<double>(S);
-    W.SM.of_rate = cv.take<double>(S);
-    W.SM.kf = cv.take<int32_t>(S);
-    W.SM.kl = cv.take<int32_t>(S);
-    W.SM.keep = cv.take<uint8_t>(S);
-    W.SM.of_has = cv.take<uint8_t>(S);
-    W.redo = cv.take<uint8_t>(S);
+    carve_series(cv, W, S);
     W.R.val = cv.take<double>(rows);
     W.R.state = cv.take<uint8_t>(rows);
     M.R2 = Rows{nullptr, nullptr};
@@ -2199,17 +2267,8 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
       M.out_emit[i] = partial ? nullptr : cv.take<uint8_t>((size_t)G * NB);
     }
     W.counts = nullptr;
-    if (n_comb > 0) {
-      W.comb = cv.take<Packed>((size_t)n_comb * kCombineSlices * NB);
-      W.comb_emit = cv.take<uint8_t>((size_t)n_comb * kCombineSlices * NB);
-    }
-    if (sel_large) {
-      W.keys = cv.take<uint64_t>((size_t)goff.back() * NB);
-      W.key_mm = cv.take<uint64_t>((size_t)((goff.back() + KT_M - 1) / KT_M) * NB * 2);
-      W.key_cnt = cv.take<uint32_t>((size_t)((goff.back() + KT_M - 1) / KT_M) * NB);
-      W.lg_kept = cv.take<uint32_t>((size_t)T.LG + 1);
-      W.sel = cv.take<SelState>((size_t)T.LG * NB);
-    }
+    if (n_comb > 0) carve_combine(cv, W, n_comb, NB);
+    if (sel_large) carve_selection(cv, W, goff.back(), T.LG, NB, false);
     return cv.off + 256;
   };
   if (part) {
@@ -2234,7 +2293,7 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
   }
   if (!P.sentinel) HIP_TRY(hipMemsetAsync(W.R.state, 0, rows, st));
   if (part) return OTSDB_OK;  // (the panel call's one pass builds the rows)
-  c->n_multi_ds = c->n_multi_group = c->n_multi_kt = c->n_multi_tf = 0;
+  multi_counters(c, 0, 0);
   rc = build_rows(c, spec, P, B, W, cells, series_row, M.rate_fused);
   if (rc) return rc;
   ++c->n_multi_ds;
@@ -2269,7 +2328,7 @@ otsdb_status multi_class_rows(otsdb_ctx* c, MultiState& M, int k, Work& Wc) {
 // slots, mask and tile partials (MA.out[j] is the caller's); who[j]: the
 // output behind launch output j
 void multi_scalar_args(const MultiState& M, int k, MultiArgs& MA, int* who) {
-  const MultiReq& q = M.q;
+  const Req& q = M.q;
   for (int i = 0; i < q.n; ++i) {
     if (M.cls[i] != k || M.kind[i] != MK_SCALAR) continue;
     const int j = MA.n_out++;
@@ -2284,7 +2343,7 @@ void multi_scalar_args(const MultiState& M, int k, MultiArgs& MA, int* who) {
 
 // Every output through the existing compaction into its own result, one
 // synchronisation, the status of the lowest-index failing output.
-otsdb_status multi_compact_launch(otsdb_ctx* c, const MultiReq& q,
+otsdb_status multi_compact_launch(otsdb_ctx* c, const Req& q,
                                   const Params& P, int64_t G,
                                   double* const* out_val,
                                   uint8_t* const* out_emit) {
@@ -2302,17 +2361,15 @@ otsdb_status multi_compact_launch(otsdb_ctx* c, const MultiReq& q,
 // The one synchronisation and the statuses of the compacted outputs.  orig:
 // the caller's index of each output (a panel call runs them grouped by
 // function); the lowest of those decides.
-otsdb_status multi_compact_wait(otsdb_ctx* c, const MultiReq& q,
+otsdb_status multi_compact_wait(otsdb_ctx* c, const Req& q,
                                 const int* orig = nullptr) {
-  hipStream_t st = c->stream;
   // (the next call of any kind clears the context's word itself: err_clean
   // stays false, as after a single query that did not end in k_compact1)
   c->small_ready = false;
   c->h_small[0] = 0;
-  HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
-                         hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const int shared = (int)(c->h_small[0] & 0xFFFFFFFF);
+  int shared;
+  const otsdb_status rs = read_err(c, &shared);
+  if (rs) return rs;
   int failed = -1;
   otsdb_status failed_rc = OTSDB_OK;
   std::string failed_msg;
@@ -2341,7 +2398,7 @@ otsdb_status multi_compact_wait(otsdb_ctx* c, const MultiReq& q,
   return failed_rc;
 }
 
-otsdb_status multi_compact_outputs(otsdb_ctx* c, const MultiReq& q,
+otsdb_status multi_compact_outputs(otsdb_ctx* c, const Req& q,
                                    const Params& P, int64_t G,
                                    double* const* out_val,
                                    uint8_t* const* out_emit) {
@@ -2356,7 +2413,7 @@ otsdb_status multi_compact_outputs(otsdb_ctx* c, const MultiReq& q,
 otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M,
                              bool compact_now = true) {
   hipStream_t st = c->stream;
-  const MultiReq& q = M.q;
+  const Req& q = M.q;
   int* const merr = c->d_merr + q.e0;  // this request's error words
   const int64_t G = M.G, NB = M.NB, S = M.S;
   Params& P = M.P;
@@ -2485,7 +2542,7 @@ otsdb_status multi_aggregate(otsdb_ctx* c, MultiState& M,
 otsdb_status multi_partials(otsdb_ctx* c, MultiState& M, Packed* partials,
                             uint8_t* emit) {
   hipStream_t st = c->stream;
-  const MultiReq& q = M.q;
+  const Req& q = M.q;
   const int64_t G = M.G, NB = M.NB, GB = G * NB;
   otsdb_status rc;
   for (int k = 0; k < M.n_cls; ++k) {
@@ -2546,11 +2603,11 @@ otsdb_status multi_partials(otsdb_ctx* c, MultiState& M, Packed* partials,
 // The outputs one after another through the single-query path (what cannot
 // share the rows): the same results, nothing shared.
 otsdb_status multi_sequential(otsdb_ctx* c, const otsdb_query_spec* spec,
-                              const MultiReq& q, const otsdb_batch* b,
+                              const Req& q, const otsdb_batch* b,
                               std::vector<int64_t>& goff) {
-  c->n_multi_ds = c->n_multi_group = c->n_multi_kt = c->n_multi_tf = 0;
+  multi_counters(c, 0, 0);
   for (int i = 0; i < q.n; ++i) {
-    const otsdb_query_spec si = multi_spec(spec, q, i);
+    const otsdb_query_spec si = req_spec(spec, q, i);
     // the "error word known zero" mark is the last single query's alone
     c->err_clean = false;
     const otsdb_status rc = run_device_impl(c, &si, b, &q.outs[i], goff);
@@ -2566,13 +2623,13 @@ otsdb_status multi_sequential(otsdb_ctx* c, const otsdb_query_spec* spec,
 }
 
 otsdb_status run_multi_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                            const MultiReq& q, const otsdb_batch* b,
+                            const Req& q, const otsdb_batch* b,
                             std::vector<int64_t>& goff) {
   c->multi_failed = -1;
   if (q.n == 1 || !(spec->ds_interval_ms > 0 || spec->run_all) ||
       anchored(spec))
     return multi_sequential(c, spec, q, b, goff);
-  const otsdb_query_spec s0 = multi_spec(spec, q, 0);
+  const otsdb_query_spec s0 = req_spec(spec, q, 0);
   Params P;
   otsdb_status rc = make_params(&s0, &P, c);
   if (rc) {
@@ -2580,11 +2637,9 @@ otsdb_status run_multi_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
     return rc;
   }
   // (a misaligned batch: the single path reports it)
-  if (((((uintptr_t)b->ts_ms) | ((uintptr_t)b->val)) & 15) ||
-      !multi_shares_rows(spec, q, P, b->n_series, goff))
+  if (misaligned(b) || !multi_shares_rows(spec, q, P, b->n_series, goff))
     return multi_sequential(c, spec, q, b, goff);
-  BatchDev B{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
-             b->series_float};
+  const BatchDev B = batch_dev(b);
   MultiState M;
   rc = multi_build(c, &s0, q, B, b->group_members, goff, P, nullptr, nullptr, M);
   if (rc) return rc;
@@ -2592,44 +2647,6 @@ otsdb_status run_multi_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
 }
 
 // ------------------------------------------------------------ panel queries
-// otsdb_agg_run_panel*: n outputs that differ in the downsampling function
-// as well as in the cross-series aggregator.  DESIGN.md §4.2.
-struct PanelReq {
-  int32_t n;
-  const int32_t* ds;
-  const int32_t* aggs;
-  const int32_t* interps;  // null: every output its aggregator's own
-  otsdb_result* outs;
-};
-
-otsdb_query_spec panel_spec(const otsdb_query_spec* s, const PanelReq& q,
-                            int i) {
-  otsdb_query_spec r = *s;
-  r.ds_agg_id = q.ds[i];
-  r.agg_id = q.aggs[i];
-  r.interp = q.interps ? q.interps[i] : OTSDB_INTERP_DEFAULT;
-  return r;
-}
-
-otsdb_status check_panel(const otsdb_query_spec* spec, const PanelReq& q) {
-  if (q.n < 1 || q.n > OTSDB_MULTI_MAX)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "n_out %d outside [1, %d]", (int)q.n,
-                OTSDB_MULTI_MAX);
-  if (!q.ds || !q.aggs)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null ds_agg_ids / agg_ids");
-  const bool ds = spec->ds_interval_ms > 0 || spec->run_all;
-  for (int i = 0; i < q.n; ++i) {
-    // (raw group-by has no downsampler: the functions are ignored)
-    if (ds && (q.ds[i] < 0 || q.ds[i] >= OTSDB_AGG_COUNT_IDS))
-      return fail(OTSDB_E_NO_SUCH_ELEMENT, "No such downsampling function: %d",
-                  q.ds[i]);
-    const otsdb_query_spec si = panel_spec(spec, q, i);
-    const otsdb_status rc = check_spec(&si);
-    if (rc) return rc;
-  }
-  return OTSDB_OK;
-}
-
 // the envelope row of a downsampling function (panel.hip), 0: not in the set
 uint32_t panel_fn(int ds) {
   switch (ds) {
@@ -2655,16 +2672,14 @@ struct PanelFunc {
   std::vector<int> idx;
   std::vector<int32_t> aggs, interps;
   std::vector<otsdb_result> outs;
-  MultiReq req(const PanelReq& q, int e0) {
-    MultiReq r{(int32_t)idx.size(), aggs.data(),
-               q.interps ? interps.data() : nullptr, outs.data()};
-    r.e0 = e0;
-    return r;
+  Req req(const Req& q, int e0) {
+    return Req{(int32_t)idx.size(), nullptr, aggs.data(),
+               q.interps ? interps.data() : nullptr, outs.data(), e0};
   }
 };
 
 std::vector<PanelFunc> panel_funcs(const otsdb_query_spec* spec,
-                                   const PanelReq& q) {
+                                   const Req& q) {
   const bool ds = spec->ds_interval_ms > 0 || spec->run_all;
   std::vector<PanelFunc> F;
   for (int i = 0; i < q.n; ++i) {
@@ -2701,6 +2716,24 @@ struct PanelOutcome {
     msg = g_last_error;
     result_short = c->result_short;
   }
+  // function f's own call (one multi call) returned r: its passes, and its
+  // totals or its failing output, both in the caller's order
+  void record(otsdb_ctx* c, const PanelFunc& f, otsdb_status r) {
+    c->n_panel_passes += c->n_multi_ds;
+    c->n_panel_mats += c->n_multi_ds;
+    if (r) return fail_at(c, f.idx[(size_t)std::max(c->multi_failed, 0)], r);
+    for (size_t j = 0; j < f.idx.size(); ++j)
+      total[f.idx[j]] = c->multi_total[j];
+  }
+  // the call's totals and status into the context
+  otsdb_status publish(otsdb_ctx* c, int n) {
+    for (int i = 0; i < n; ++i) c->multi_total[i] = total[i];
+    if (failed < 0) return OTSDB_OK;
+    c->multi_failed = failed;
+    c->result_short = result_short;
+    g_last_error = msg;
+    return rc;
+  }
 };
 
 // The envelope functions E of a request as one pass: every function's request,
@@ -2708,10 +2741,10 @@ struct PanelOutcome {
 struct PanelPass {
   std::vector<MultiState> MS;
   std::vector<otsdb_query_spec> sp;
-  std::vector<MultiReq> qs;
+  std::vector<Req> qs;
   std::vector<int> orig;
   std::vector<otsdb_result> outs;
-  PanelPass(const otsdb_query_spec* spec, const PanelReq& q,
+  PanelPass(const otsdb_query_spec* spec, const Req& q,
             std::vector<PanelFunc*>& E)
       : MS(E.size()), sp(E.size(), *spec), qs(E.size()) {
     for (size_t d = 0; d < E.size(); ++d) {
@@ -2753,7 +2786,7 @@ otsdb_status panel_build(otsdb_ctx* c, PanelPass& X, const BatchDev& B,
   HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(int), st));
   HIP_TRY(hipMemsetAsync(c->d_merr, 0, OTSDB_MULTI_MAX * sizeof(int), st));
   c->clean_entry = false;
-  c->n_multi_ds = c->n_multi_group = c->n_multi_kt = c->n_multi_tf = 0;
+  multi_counters(c, 0, 0);
   return OTSDB_OK;
 }
 
@@ -2771,7 +2804,8 @@ otsdb_status panel_finish(otsdb_ctx* c, PanelPass& X, PanelOutcome& O) {
                               X.MS[d].out_val, X.MS[d].out_emit);
     if (rc) return rc;
   }
-  const MultiReq all{(int32_t)X.orig.size(), nullptr, nullptr, X.outs.data()};
+  const Req all{(int32_t)X.orig.size(), nullptr, nullptr, nullptr,
+                X.outs.data()};
   rc = multi_compact_wait(c, all, X.orig.data());
   for (size_t j = 0; j < X.orig.size(); ++j)
     O.total[X.orig[j]] = c->multi_total[X.orig[j]];
@@ -2784,13 +2818,12 @@ otsdb_status panel_finish(otsdb_ctx* c, PanelPass& X, PanelOutcome& O) {
 // envelope kernel into the D row matrices, the existing multi_aggregate over
 // each matrix, every output compacted, one synchronisation.
 otsdb_status panel_shared(otsdb_ctx* c, const otsdb_query_spec* spec,
-                          const PanelReq& q, const otsdb_batch* b,
+                          const Req& q, const otsdb_batch* b,
                           std::vector<int64_t>& goff, const Params& P,
                           std::vector<PanelFunc*>& E, PanelOutcome& O) {
   hipStream_t st = c->stream;
   const int D = (int)E.size();
-  BatchDev B{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
-             b->series_float};
+  const BatchDev B = batch_dev(b);
   PanelPass X(spec, q, E);
   std::vector<MultiState>& MS = X.MS;
   otsdb_status rc = panel_build(c, X, B, b->group_members, goff, P, nullptr);
@@ -2840,8 +2873,35 @@ otsdb_status panel_shared(otsdb_ctx* c, const otsdb_query_spec* spec,
   return panel_finish(c, X, O);
 }
 
+// the envelope functions of a request's functions F
+std::vector<PanelFunc*> panel_envelope(std::vector<PanelFunc>& F) {
+  std::vector<PanelFunc*> E;
+  for (PanelFunc& f : F)
+    if (f.fn) E.push_back(&f);
+  return E;
+}
+
+// What the columnar and the cells call ask alike before the envelope
+// functions E share one pass: two or more of them, a query without rate or
+// per-series anchors, and every function's outputs within the budgets of the
+// |E| row matrices together.  *P: the grid (of E[0]'s first output).
+bool panel_shares_rows(otsdb_ctx* c, const otsdb_query_spec* spec, const Req& q,
+                       std::vector<PanelFunc*>& E, int64_t S,
+                       const std::vector<int64_t>& goff, Params* P) {
+  if (E.size() < 2 || spec->rate || anchored(spec)) return false;
+  const otsdb_query_spec s0 = req_spec(spec, q, E[0]->idx[0]);
+  if (make_params(&s0, P, c) != OTSDB_OK) return false;  // (the calls report it)
+  for (PanelFunc* f : E) {
+    otsdb_query_spec sd = *spec;
+    sd.ds_agg_id = f->ds;
+    if (!multi_shares_rows(&sd, f->req(q, 0), *P, S, goff, 1, (int)E.size()))
+      return false;
+  }
+  return true;
+}
+
 otsdb_status run_panel_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                            const PanelReq& q, const otsdb_batch* b,
+                            const Req& q, const otsdb_batch* b,
                             std::vector<int64_t>& goff) {
   c->multi_failed = -1;
   c->n_panel_passes = c->n_panel_mats = 0;
@@ -2849,22 +2909,10 @@ otsdb_status run_panel_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   PanelOutcome O;
   // ---- the shared pass: two or more envelope functions of a downsampled,
   // columnar query without rate or per-series anchors, within the budgets
-  std::vector<PanelFunc*> E;
-  for (PanelFunc& f : F)
-    if (f.fn) E.push_back(&f);
-  bool shared = E.size() >= 2 && !spec->rate && !anchored(spec) &&
-                !((((uintptr_t)b->ts_ms) | ((uintptr_t)b->val)) & 15);
+  std::vector<PanelFunc*> E = panel_envelope(F);
   Params P;
-  if (shared) {
-    const otsdb_query_spec s0 = panel_spec(spec, q, E[0]->idx[0]);
-    shared = make_params(&s0, &P, c) == OTSDB_OK;  // (else: the calls report it)
-  }
-  for (size_t d = 0; shared && d < E.size(); ++d) {
-    otsdb_query_spec sd = *spec;
-    sd.ds_agg_id = E[d]->ds;
-    shared = multi_shares_rows(&sd, E[d]->req(q, 0), P, b->n_series, goff, 1,
-                               (int)E.size());
-  }
+  const bool shared = !misaligned(b) &&
+                      panel_shares_rows(c, spec, q, E, b->n_series, goff, &P);
   if (shared) {
     const otsdb_status rc = panel_shared(c, spec, q, b, goff, P, E, O);
     if (rc) return rc;  // (the device or the workspace, not an output)
@@ -2875,23 +2923,9 @@ otsdb_status run_panel_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
     otsdb_query_spec sf = *spec;
     sf.ds_agg_id = f.ds;
     c->result_short = false;
-    const otsdb_status rc = run_multi_impl(c, &sf, f.req(q, 0), b, goff);
-    c->n_panel_passes += c->n_multi_ds;
-    c->n_panel_mats += c->n_multi_ds;
-    if (rc) {
-      const int j = c->multi_failed >= 0 ? c->multi_failed : 0;
-      O.fail_at(c, f.idx[(size_t)j], rc);
-      continue;
-    }
-    for (size_t j = 0; j < f.idx.size(); ++j)
-      O.total[f.idx[j]] = c->multi_total[j];
+    O.record(c, f, run_multi_impl(c, &sf, f.req(q, 0), b, goff));
   }
-  for (int i = 0; i < q.n; ++i) c->multi_total[i] = O.total[i];
-  if (O.failed < 0) return OTSDB_OK;
-  c->multi_failed = O.failed;
-  c->result_short = O.result_short;
-  g_last_error = O.msg;
-  return O.rc;
+  return O.publish(c, q.n);
 }
 
 // otsdb_decode_cells_device without the lock (also the fallback of the
@@ -3040,6 +3074,71 @@ otsdb_status requal_impl(otsdb_ctx* c, const CellsDev& C, CellsDev* out,
 otsdb_status cells_columnar(otsdb_ctx* c, const otsdb_cells* cells,
                             const otsdb_batch* b, otsdb_batch* cb_out);
 
+// The fused cells path with its retries, for every cells query.  pass(CQ,
+// series_row): one attempt's launches over the columns CQ; finish(): the
+// rest of the query, once the attempt's error word is clean.
+// A column the fused path does not take (ERR_CELLS_GENERIC) — widths mixed
+// inside a row or across a series' rows — is rewritten with 4-byte
+// qualifiers (k_requal) and the fused path runs again; what it still does
+// not take re-runs through the caller's decode.  A uniform fold that meets a
+// qualifier of other flags is run again with the general kernel
+// (ERR_CELLS_NONUNI, one more attempt).
+// *end: whether the status is the query's (CELLS_CORRUPT: of a corrupt
+// column) or the caller decodes (CELLS_DECODE).
+enum CellsEnd { CELLS_DONE, CELLS_CORRUPT, CELLS_DECODE };
+
+template <class Pass, class Finish>
+otsdb_status cells_attempts(otsdb_ctx* c, const otsdb_cells* cells, int64_t S,
+                            Params& P, CellsEnd* end, Pass pass,
+                            Finish finish) {
+  hipStream_t st = c->stream;
+  const int64_t R = cells->n_rows;
+  *end = CELLS_DONE;
+  otsdb_status rc = ensure(&c->cells_ws, &c->cells_ws_cap, (size_t)(S + 1) * 8);
+  if (rc) return rc;
+  int64_t* series_row = (int64_t*)c->cells_ws;
+  hipLaunchKernelGGL(k_series_rows, dim3(blocks_for(R + 1, 256)), dim3(256),
+                     0, st, R, S, cells->row_series, series_row);
+  P.check_order = c->verbatim ? 1 : 0;
+  const CellsDev C{R, cells->row_series, cells->row_base_s, cells->qual_off,
+                   cells->qual, cells->val_off, cells->val};
+  CellsDev CQ = C;
+  c->cells_no_uni = false;
+  bool requaled = false;
+  for (int attempt = 0; attempt < 4; ++attempt) {
+    rc = pass(CQ, series_row);
+    if (rc) return rc;
+    int e;
+    if ((rc = read_err(c, &e))) return rc;
+    if ((e & ERR_CELLS_NONUNI) && !c->cells_no_uni) {
+      ++c->n_cells_uni_miss;
+      c->cells_no_uni = true;
+      continue;
+    }
+    if (c->verbatim && (e & (ERR_CORRUPT_CELL | ERR_CELLS_GENERIC |
+                             ERR_NOT_SORTED | ERR_SPEC_MISS)))
+      return spec_miss(c);
+    if (e & ERR_CORRUPT_CELL) {
+      *end = CELLS_CORRUPT;
+      return fail(OTSDB_E_ILLEGAL_DATA,
+                  "Corrupted value: couldn't break down into individual values");
+    }
+    if (!(e & ERR_CELLS_GENERIC)) return finish();
+    if (requaled) break;
+    requaled = true;
+    c->cells_no_uni = false;
+    {
+      StageTimer rq_tm(c, 7);
+      rc = requal_impl(c, C, &CQ, st);
+      if (rc) return rc;
+    }
+  }
+  c->cells_no_uni = false;
+  if (c->verbatim) return spec_miss(c);  // (they have no decode to fall back to)
+  *end = CELLS_DECODE;
+  return OTSDB_OK;
+}
+
 // Query straight from compacted columns: the fused decode + downsample when
 // the query and the columns allow it, else decode -> columnar -> pipeline.
 // mq: several aggregators (otsdb_agg_run_cells_multi_device; `spec` carries
@@ -3049,10 +3148,9 @@ otsdb_status cells_columnar(otsdb_ctx* c, const otsdb_cells* cells,
 otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
                             const otsdb_cells* cells, const otsdb_batch* b,
                             otsdb_result* out, std::vector<int64_t>& goff,
-                            const MultiReq* mq = nullptr) {
+                            const Req* mq = nullptr) {
   otsdb_status rc = check_spec(spec);
   if (rc) return rc;
-  hipStream_t st = c->stream;
   const int64_t S = b->n_series, R = cells->n_rows;
   if (S < 0 || R < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
   const bool ds = spec->ds_interval_ms > 0 || spec->run_all;
@@ -3063,68 +3161,32 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
     rc = make_params(spec, &P, c);
     if (rc) return rc;
   }
-  CellsDev C{R, cells->row_series, cells->row_base_s, cells->qual_off,
-             cells->qual, cells->val_off, cells->val};
   if (fused && !P.ds_sel && !P.run_all &&
       (!mq || multi_shares_rows(spec, *mq, P, S, goff))) {
-    rc = ensure(&c->cells_ws, &c->cells_ws_cap, (size_t)(S + 1) * 8);
-    if (rc) return rc;
-    int64_t* series_row = (int64_t*)c->cells_ws;
-    hipLaunchKernelGGL(k_series_rows, dim3(blocks_for(R + 1, 256)), dim3(256),
-                       0, st, R, S, cells->row_series, series_row);
-    BatchDev B{S, nullptr, nullptr, nullptr, nullptr, nullptr};
-    P.check_order = c->verbatim ? 1 : 0;
-    // a column the fused path does not take (ERR_CELLS_GENERIC) — widths
-    // mixed inside a row or across a series' rows — is rewritten with
-    // 4-byte qualifiers (k_requal) and the fused path runs again; what it
-    // still does not take re-runs through the decode below
-    // (a uniform fold that meets a qualifier of other flags is run again
-    // with the general kernel: ERR_CELLS_NONUNI, one more attempt)
-    CellsDev CQ = C;
-    c->cells_no_uni = false;
-    bool requaled = false;
-    for (int attempt = 0; attempt < 4; ++attempt) {
-      Work W;
-      MultiState MS;
-      if (mq)
-        rc = multi_build(c, spec, *mq, B, b->group_members, goff, P, &CQ,
-                         series_row, MS);
-      else
-        rc = run_pipeline(c, spec, B, b->group_members, goff, P, W, 0, nullptr,
-                          nullptr, &CQ, series_row);
-      if (rc) return rc;
-      HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
-                             hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      const int e = (int)(c->h_small[0] & 0xFFFFFFFF);
-      if ((e & ERR_CELLS_NONUNI) && !c->cells_no_uni) {
-        ++c->n_cells_uni_miss;
-        c->cells_no_uni = true;
-        continue;
-      }
-      if (c->verbatim && (e & (ERR_CORRUPT_CELL | ERR_CELLS_GENERIC |
-                               ERR_NOT_SORTED | ERR_SPEC_MISS)))
-        return spec_miss(c);
-      if (e & ERR_CORRUPT_CELL)
-        return fail(OTSDB_E_ILLEGAL_DATA,
-                    "Corrupted value: couldn't break down into individual values");
-      if (!(e & ERR_CELLS_GENERIC)) {
-        if (mq) return multi_aggregate(c, MS);
-        const int64_t G = (int64_t)goff.size() - 1;
-        rc = compact(c, P, G, W.out_val, W.out_emit, W.counts, out);
-        if (rc) return rc;
-        return finish(c, G, out);
-      }
-      if (requaled) break;
-      requaled = true;
-      c->cells_no_uni = false;
-      {
-        std::unique_ptr<StageTimer> rq_tm(new StageTimer(c, 7));
-        rc = requal_impl(c, C, &CQ, st);
-        if (rc) return rc;
-      }
-    }
-    c->cells_no_uni = false;
+    const BatchDev B{S, nullptr, nullptr, nullptr, nullptr, nullptr};
+    Work W;
+    MultiState MS;
+    CellsEnd end;
+    rc = cells_attempts(
+        c, cells, S, P, &end,
+        [&](const CellsDev& CQ, const int64_t* series_row) {
+          if (mq) {  // (every attempt its own work set)
+            MS = MultiState();
+            return multi_build(c, spec, *mq, B, b->group_members, goff, P, &CQ,
+                               series_row, MS);
+          }
+          W = Work();
+          return run_pipeline(c, spec, B, b->group_members, goff, P, W, 0,
+                              nullptr, nullptr, &CQ, series_row);
+        },
+        [&]() {
+          if (mq) return multi_aggregate(c, MS);
+          const int64_t G = (int64_t)goff.size() - 1;
+          const otsdb_status rf =
+              compact(c, P, G, W.out_val, W.out_emit, W.counts, out);
+          return rf ? rf : finish(c, G, out);
+        });
+    if (rc || end != CELLS_DECODE) return rc;
   }
   // (verbatim storage rows take only the cells fold)
   if (c->verbatim) return spec_miss(c);
@@ -3136,6 +3198,20 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   if (rc) return rc;
   if (mq) return run_multi_impl(c, spec, *mq, &cb, goff);
   return run_device_impl(c, spec, &cb, out, goff);
+}
+
+// One cells call for a request without downsampling functions: the single
+// query, unchanged, for one output, else the cells multi call.
+otsdb_status run_cells_req(otsdb_ctx* c, const otsdb_query_spec* spec,
+                           const Req& q, const otsdb_cells* cells,
+                           const otsdb_batch* b, std::vector<int64_t>& goff) {
+  const otsdb_query_spec s0 = req_spec(spec, q, 0);
+  c->multi_failed = -1;
+  if (q.n > 1) return run_cells_impl(c, &s0, cells, b, nullptr, goff, &q);
+  multi_counters(c, 1, 1);
+  const otsdb_status rc = run_cells_impl(c, &s0, cells, b, &q.outs[0], goff);
+  if (!rc) c->multi_total[0] = c->h_small[1];
+  return rc;
 }
 
 // The compacted columns decoded into the context's own columnar buffer: *cb
@@ -3221,19 +3297,19 @@ otsdb_status cells_panel_rows(otsdb_ctx* c, PanelPass& X,
 // otsdb_agg_run_cells_panel_device: run_cells_impl's routing for a panel
 // request.  Two or more envelope functions of a query the fused cells path
 // takes share one pass over the compacted columns (the decode runs once for
-// all of them), inside run_cells_impl's attempt loop: a column of mixed
-// qualifier widths is rewritten once and the pass runs again, a corrupt one
-// fails every output.  The other functions of such a request then run one
-// cells call each.  One distinct function is the cells multi call.  What the
+// all of them), inside the attempt loop of every cells query
+// (cells_attempts): a column of mixed qualifier widths is rewritten once and
+// the pass runs again, a corrupt one fails every output.  The other
+// functions of such a request then run one cells call each.  One distinct
+// function is the cells multi call.  What the
 // fused path does not take (`all`, anchored calendars, rate, raw group-by,
 // grids past the limits, columns still generic after the rewrite) is decoded
 // once into the context's columnar buffer and runs as the columnar panel
 // call.
 otsdb_status run_cells_panel_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                                  const PanelReq& q, const otsdb_cells* cells,
+                                  const Req& q, const otsdb_cells* cells,
                                   const otsdb_batch* b,
                                   std::vector<int64_t>& goff) {
-  hipStream_t st = c->stream;
   const int64_t S = b->n_series, R = cells->n_rows;
   if (S < 0 || R < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
   c->multi_failed = -1;
@@ -3244,110 +3320,40 @@ otsdb_status run_cells_panel_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   auto run_func = [&](PanelFunc& f) {
     otsdb_query_spec sf = *spec;
     sf.ds_agg_id = f.ds;
-    const MultiReq mq = f.req(q, 0);
-    sf.agg_id = mq.aggs[0];
-    sf.interp = mq.interps ? mq.interps[0] : OTSDB_INTERP_DEFAULT;
     c->result_short = false;
-    c->multi_failed = -1;
-    otsdb_status rc;
-    if (mq.n == 1) {
-      c->n_multi_ds = c->n_multi_group = 1;
-      c->n_multi_kt = c->n_multi_tf = 0;
-      rc = run_cells_impl(c, &sf, cells, b, &mq.outs[0], goff);
-      if (!rc) c->multi_total[0] = c->h_small[1];
-    } else {
-      rc = run_cells_impl(c, &sf, cells, b, nullptr, goff, &mq);
-    }
-    c->n_panel_passes += c->n_multi_ds;
-    c->n_panel_mats += c->n_multi_ds;
-    if (rc) {
-      const int j = c->multi_failed >= 0 ? c->multi_failed : 0;
-      O.fail_at(c, f.idx[(size_t)j], rc);
-      return;
-    }
-    for (size_t j = 0; j < f.idx.size(); ++j)
-      O.total[f.idx[j]] = c->multi_total[j];
+    O.record(c, f, run_cells_req(c, &sf, f.req(q, 0), cells, b, goff));
   };
-  auto outcome = [&]() -> otsdb_status {
-    for (int i = 0; i < q.n; ++i) c->multi_total[i] = O.total[i];
-    if (O.failed < 0) return OTSDB_OK;
-    c->multi_failed = O.failed;
-    c->result_short = O.result_short;
-    g_last_error = O.msg;
-    return O.rc;
-  };
-  std::vector<PanelFunc*> E;
-  for (PanelFunc& f : F)
-    if (f.fn) E.push_back(&f);
+  std::vector<PanelFunc*> E = panel_envelope(F);
   const bool ds = spec->ds_interval_ms > 0 || spec->run_all;
-  bool shared = ds && E.size() >= 2 && !spec->rate && !spec->run_all &&
-                !anchored(spec);
   Params P;
+  const bool shared = ds && !spec->run_all &&
+                      panel_shares_rows(c, spec, q, E, S, goff, &P) &&
+                      !P.ds_sel && !P.run_all;
   if (shared) {
-    const otsdb_query_spec s0 = panel_spec(spec, q, E[0]->idx[0]);
-    shared = make_params(&s0, &P, c) == OTSDB_OK && !P.ds_sel && !P.run_all;
-  }
-  for (size_t d = 0; shared && d < E.size(); ++d) {
-    otsdb_query_spec sd = *spec;
-    sd.ds_agg_id = E[d]->ds;
-    shared = multi_shares_rows(&sd, E[d]->req(q, 0), P, S, goff, 1,
-                               (int)E.size());
-  }
-  if (shared) {
-    otsdb_status rc = ensure(&c->cells_ws, &c->cells_ws_cap, (size_t)(S + 1) * 8);
-    if (rc) return rc;
-    int64_t* series_row = (int64_t*)c->cells_ws;
-    hipLaunchKernelGGL(k_series_rows, dim3(blocks_for(R + 1, 256)), dim3(256),
-                       0, st, R, S, cells->row_series, series_row);
-    BatchDev B{S, nullptr, nullptr, nullptr, nullptr, nullptr};
-    P.check_order = c->verbatim ? 1 : 0;
-    const CellsDev C{R, cells->row_series, cells->row_base_s, cells->qual_off,
-                     cells->qual, cells->val_off, cells->val};
-    CellsDev CQ = C;
+    const BatchDev B{S, nullptr, nullptr, nullptr, nullptr, nullptr};
     PanelPass X(spec, q, E);
-    bool requaled = false, done = false;
-    // run_cells_impl's attempts (the row kernel raises no ERR_CELLS_NONUNI:
-    // at most the pass, the rewrite, the pass again)
-    for (int attempt = 0; attempt < 4 && !done; ++attempt) {
-      rc = cells_panel_rows(c, X, E, B, b->group_members, goff, P, CQ,
-                            series_row);
-      if (rc) return rc;
-      HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
-                             hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      const int e = (int)(c->h_small[0] & 0xFFFFFFFF);
-      if (e & ERR_CELLS_NONUNI) continue;
-      if (c->verbatim && (e & (ERR_CORRUPT_CELL | ERR_CELLS_GENERIC |
-                               ERR_NOT_SORTED | ERR_SPEC_MISS)))
-        return spec_miss(c);
-      if (e & ERR_CORRUPT_CELL) {
-        // the columns are every output's: all fail, the lowest index reports
-        c->multi_failed = 0;
-        return fail(OTSDB_E_ILLEGAL_DATA,
-                    "Corrupted value: couldn't break down into individual values");
-      }
-      if (!(e & ERR_CELLS_GENERIC)) {
-        rc = panel_finish(c, X, O);
-        if (rc) return rc;
-        done = true;
-        break;
-      }
-      if (requaled) break;
-      requaled = true;
-      std::unique_ptr<StageTimer> rq_tm(new StageTimer(c, 7));
-      rc = requal_impl(c, C, &CQ, st);
-      if (rc) return rc;
-    }
-    if (done) {
+    CellsEnd end;
+    // cells_attempts (the row kernel raises no ERR_CELLS_NONUNI: at most the
+    // pass, the rewrite, the pass again)
+    const otsdb_status rc = cells_attempts(
+        c, cells, S, P, &end,
+        [&](const CellsDev& CQ, const int64_t* series_row) {
+          return cells_panel_rows(c, X, E, B, b->group_members, goff, P, CQ,
+                                  series_row);
+        },
+        [&]() { return panel_finish(c, X, O); });
+    // the columns are every output's: all fail, the lowest index reports
+    if (end == CELLS_CORRUPT) c->multi_failed = 0;
+    if (rc) return rc;
+    if (end == CELLS_DONE) {
       for (PanelFunc& f : F)
         if (!f.fn) run_func(f);
-      return outcome();
+      return O.publish(c, q.n);
     }
-    if (c->verbatim) return spec_miss(c);
     c->n_panel_passes = c->n_panel_mats = 0;
   } else if (F.size() == 1) {
     run_func(F[0]);
-    return outcome();
+    return O.publish(c, q.n);
   }
   // one decode for the whole panel, then the columnar panel call
   otsdb_batch cb;
@@ -3964,13 +3970,8 @@ otsdb_status otsdb_agg_run_device(otsdb_ctx* c, const otsdb_query_spec* spec,
                                   const otsdb_batch* b, otsdb_result* out,
                                   void* hip_stream) {
   if (!c || !spec || !b || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  StreamBinding bind(c, hip_stream);
-  std::vector<int64_t> goff;
-  otsdb_status rc = read_goff(c, b, true, goff);
-  if (!rc) rc = run_device_impl(c, spec, b, out, goff);
-  return rc;
+  DeviceCall dc(c, b, hip_stream);
+  return dc.rc ? dc.rc : run_device_impl(c, spec, b, out, dc.goff);
 }
 
 otsdb_status otsdb_agg_run_cells_device(otsdb_ctx* c,
@@ -3980,22 +3981,16 @@ otsdb_status otsdb_agg_run_cells_device(otsdb_ctx* c,
                                         otsdb_result* out, void* hip_stream) {
   if (!c || !spec || !cells || !b || !out)
     return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  StreamBinding bind(c, hip_stream);
-  std::vector<int64_t> goff;
-  otsdb_status rc = read_goff(c, b, true, goff);
-  if (!rc) rc = run_cells_impl(c, spec, cells, b, out, goff);
-  return rc;
+  DeviceCall dc(c, b, hip_stream);
+  return dc.rc ? dc.rc : run_cells_impl(c, spec, cells, b, out, dc.goff);
 }
 
-// The host-pointer entries: the batch staged in HBM once, n results (mq / pq:
-// the multi-aggregator / panel request whose results `outs` are, else one
+// The host-pointer entries: the batch staged in HBM once, n results (q: the
+// multi-aggregator or panel request whose results `outs` are, null: one
 // single query).
 static otsdb_status run_host(otsdb_ctx* c, const otsdb_query_spec* spec,
                              const otsdb_batch* b, int n, otsdb_result* outs,
-                             const MultiReq* mq,
-                             const PanelReq* pq = nullptr) {
+                             const Req* q) {
   CtxLock lk(c);
   HIP_TRY(hipSetDevice(c->device));
   std::vector<int64_t> goff;
@@ -4062,15 +4057,12 @@ static otsdb_status run_host(otsdb_ctx* c, const otsdb_query_spec* spec,
     dr[i].is_int = (uint8_t*)pp[10 + 4 * i];
   }
   c->result_short = false;
-  const bool many = mq || pq;
-  if (pq) {
-    PanelReq dq = *pq;
+  const bool many = q != nullptr;
+  if (many) {
+    Req dq = *q;
     dq.outs = dr.data();
-    rc = run_panel_impl(c, spec, dq, &db, goff);
-  } else if (mq) {
-    MultiReq dq = *mq;
-    dq.outs = dr.data();
-    rc = run_multi_impl(c, spec, dq, &db, goff);
+    rc = dq.ds ? run_panel_impl(c, spec, dq, &db, goff)
+               : run_multi_impl(c, spec, dq, &db, goff);
   } else {
     rc = run_device_impl(c, spec, &db, &dr[0], goff);
   }
@@ -4103,26 +4095,30 @@ otsdb_status otsdb_agg_run(otsdb_ctx* c, const otsdb_query_spec* spec,
   return run_host(c, spec, b, 1, out, nullptr);
 }
 
+// otsdb_agg_plan_multi's bound of a call's workspace: the downsampler's rows
+// and one class matrix, every output's dense results and one tile partial
+// per distinct reduction state
+static int64_t multi_workspace_bytes(const otsdb_batch* b, int64_t nb,
+                                     int64_t n_out) {
+  return b->n_series * (nb * 18 + 48) +
+         (n_out + 1) * b->n_groups * (nb * 9 + 8) +
+         (int64_t)kMultiSlots * (b->n_series / kChunk + b->n_groups) * nb * 33;
+}
+
 otsdb_status otsdb_agg_plan_multi(otsdb_ctx* c, const otsdb_query_spec* spec,
                                   int32_t n_out, const int32_t* agg_ids,
                                   const int32_t* interps, const otsdb_batch* b,
                                   otsdb_sizes* out) {
   if (!spec || !b || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  const MultiReq q{n_out, agg_ids, interps, nullptr};
-  otsdb_status rc = check_multi(spec, q);
+  const Req q{n_out, nullptr, agg_ids, interps, nullptr};
+  otsdb_status rc = check_req(spec, q);
   if (rc) return rc;
-  const otsdb_query_spec s0 = multi_spec(spec, q, 0);
+  const otsdb_query_spec s0 = req_spec(spec, q, 0);
   rc = otsdb_agg_plan(c, &s0, b, out);
   if (rc) return rc;
-  // the bound of the point count holds for each output; the workspace: the
-  // downsampler's rows and one class matrix, every output's dense results
-  // and one tile partial per distinct reduction state
+  // the bound of the point count holds for each output
   if (s0.ds_interval_ms > 0 || s0.run_all)
-    out->workspace_bytes =
-        b->n_series * (out->n_buckets * 18 + 48) +
-        (int64_t)(n_out + 1) * b->n_groups * (out->n_buckets * 9 + 8) +
-        (int64_t)kMultiSlots * (b->n_series / kChunk + b->n_groups) *
-            out->n_buckets * 33;
+    out->workspace_bytes = multi_workspace_bytes(b, out->n_buckets, n_out);
   return OTSDB_OK;
 }
 
@@ -4133,16 +4129,11 @@ otsdb_status otsdb_agg_run_multi_device(otsdb_ctx* c,
                                         const otsdb_batch* b,
                                         otsdb_result* outs, void* hip_stream) {
   if (!c || !spec || !b || !outs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  const MultiReq q{n_out, agg_ids, interps, outs};
-  otsdb_status rc = check_multi(spec, q);
+  const Req q{n_out, nullptr, agg_ids, interps, outs};
+  otsdb_status rc = check_req(spec, q);
   if (rc) return rc;
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  StreamBinding bind(c, hip_stream);
-  std::vector<int64_t> goff;
-  rc = read_goff(c, b, true, goff);
-  if (!rc) rc = run_multi_impl(c, spec, q, b, goff);
-  return rc;
+  DeviceCall dc(c, b, hip_stream);
+  return dc.rc ? dc.rc : run_multi_impl(c, spec, q, b, dc.goff);
 }
 
 otsdb_status otsdb_agg_run_multi(otsdb_ctx* c, const otsdb_query_spec* spec,
@@ -4150,8 +4141,8 @@ otsdb_status otsdb_agg_run_multi(otsdb_ctx* c, const otsdb_query_spec* spec,
                                  const int32_t* interps, const otsdb_batch* b,
                                  otsdb_result* outs) {
   if (!c || !spec || !b || !outs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  const MultiReq q{n_out, agg_ids, interps, outs};
-  const otsdb_status rc = check_multi(spec, q);
+  const Req q{n_out, nullptr, agg_ids, interps, outs};
+  const otsdb_status rc = check_req(spec, q);
   if (rc) return rc;
   return run_host(c, spec, b, n_out, outs, &q);
 }
@@ -4162,22 +4153,17 @@ otsdb_status otsdb_agg_plan_panel(otsdb_ctx* c, const otsdb_query_spec* spec,
                                   const int32_t* interps, const otsdb_batch* b,
                                   otsdb_sizes* out) {
   if (!spec || !b || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  const PanelReq q{n_out, ds_agg_ids, agg_ids, interps, nullptr};
-  otsdb_status rc = check_panel(spec, q);
+  const Req q{n_out, ds_agg_ids, agg_ids, interps, nullptr};
+  otsdb_status rc = check_req(spec, q, /*panel=*/true);
   if (rc) return rc;
-  const otsdb_query_spec s0 = panel_spec(spec, q, 0);
+  const otsdb_query_spec s0 = req_spec(spec, q, 0);
   rc = otsdb_agg_plan(c, &s0, b, out);
   if (rc) return rc;
   // the bound of the point count holds for each output; the workspace: per
   // distinct function what plan_multi counts for its outputs (at most n_out
   // functions of one output each)
   if (s0.ds_interval_ms > 0 || s0.run_all)
-    out->workspace_bytes =
-        (int64_t)n_out *
-        (b->n_series * (out->n_buckets * 18 + 48) +
-         (int64_t)2 * b->n_groups * (out->n_buckets * 9 + 8) +
-         (int64_t)kMultiSlots * (b->n_series / kChunk + b->n_groups) *
-             out->n_buckets * 33);
+    out->workspace_bytes = n_out * multi_workspace_bytes(b, out->n_buckets, 1);
   return OTSDB_OK;
 }
 
@@ -4190,16 +4176,11 @@ otsdb_status otsdb_agg_run_panel_device(otsdb_ctx* c,
                                         const otsdb_batch* b,
                                         otsdb_result* outs, void* hip_stream) {
   if (!c || !spec || !b || !outs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  const PanelReq q{n_out, ds_agg_ids, agg_ids, interps, outs};
-  otsdb_status rc = check_panel(spec, q);
+  const Req q{n_out, ds_agg_ids, agg_ids, interps, outs};
+  otsdb_status rc = check_req(spec, q, /*panel=*/true);
   if (rc) return rc;
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  StreamBinding bind(c, hip_stream);
-  std::vector<int64_t> goff;
-  rc = read_goff(c, b, true, goff);
-  if (!rc) rc = run_panel_impl(c, spec, q, b, goff);
-  return rc;
+  DeviceCall dc(c, b, hip_stream);
+  return dc.rc ? dc.rc : run_panel_impl(c, spec, q, b, dc.goff);
 }
 
 otsdb_status otsdb_agg_run_panel(otsdb_ctx* c, const otsdb_query_spec* spec,
@@ -4207,10 +4188,10 @@ otsdb_status otsdb_agg_run_panel(otsdb_ctx* c, const otsdb_query_spec* spec,
                                  const int32_t* agg_ids, const int32_t* interps,
                                  const otsdb_batch* b, otsdb_result* outs) {
   if (!c || !spec || !b || !outs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  const PanelReq q{n_out, ds_agg_ids, agg_ids, interps, outs};
-  const otsdb_status rc = check_panel(spec, q);
+  const Req q{n_out, ds_agg_ids, agg_ids, interps, outs};
+  const otsdb_status rc = check_req(spec, q, /*panel=*/true);
   if (rc) return rc;
-  return run_host(c, spec, b, n_out, outs, nullptr, &q);
+  return run_host(c, spec, b, n_out, outs, &q);
 }
 
 otsdb_status otsdb_agg_run_cells_multi_device(
@@ -4219,23 +4200,11 @@ otsdb_status otsdb_agg_run_cells_multi_device(
     const otsdb_batch* b, otsdb_result* outs, void* hip_stream) {
   if (!c || !spec || !cells || !b || !outs)
     return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  const MultiReq q{n_out, agg_ids, interps, outs};
-  otsdb_status rc = check_multi(spec, q);
+  const Req q{n_out, nullptr, agg_ids, interps, outs};
+  otsdb_status rc = check_req(spec, q);
   if (rc) return rc;
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  StreamBinding bind(c, hip_stream);
-  std::vector<int64_t> goff;
-  rc = read_goff(c, b, true, goff);
-  if (rc) return rc;
-  const otsdb_query_spec s0 = multi_spec(spec, q, 0);
-  c->multi_failed = -1;
-  if (n_out == 1) {  // the single query, unchanged
-    c->n_multi_ds = c->n_multi_group = 1;
-    c->n_multi_kt = c->n_multi_tf = 0;
-    return run_cells_impl(c, &s0, cells, b, &outs[0], goff);
-  }
-  return run_cells_impl(c, &s0, cells, b, nullptr, goff, &q);
+  DeviceCall dc(c, b, hip_stream);
+  return dc.rc ? dc.rc : run_cells_req(c, spec, q, cells, b, dc.goff);
 }
 
 otsdb_status otsdb_agg_run_cells_panel_device(
@@ -4245,16 +4214,11 @@ otsdb_status otsdb_agg_run_cells_panel_device(
     void* hip_stream) {
   if (!c || !spec || !cells || !b || !outs)
     return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  const PanelReq q{n_out, ds_agg_ids, agg_ids, interps, outs};
-  otsdb_status rc = check_panel(spec, q);
+  const Req q{n_out, ds_agg_ids, agg_ids, interps, outs};
+  otsdb_status rc = check_req(spec, q, /*panel=*/true);
   if (rc) return rc;
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  StreamBinding bind(c, hip_stream);
-  std::vector<int64_t> goff;
-  rc = read_goff(c, b, true, goff);
-  if (rc) return rc;
-  return run_cells_panel_impl(c, spec, q, cells, b, goff);
+  DeviceCall dc(c, b, hip_stream);
+  return dc.rc ? dc.rc : run_cells_panel_impl(c, spec, q, cells, b, dc.goff);
 }
 
 }  // extern "C"
@@ -4283,8 +4247,7 @@ otsdb_status partials_locked(otsdb_ctx* c, const otsdb_query_spec* spec,
   Params P;
   otsdb_status rc = partials_grid(c, spec, b, &P);
   if (!rc) {
-    BatchDev B{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
-               b->series_float};
+    const BatchDev B = batch_dev(b);
     Work W;
     const int64_t G = (int64_t)goff.size() - 1;
     if (G * P.nb > 0 && init) {
@@ -4304,15 +4267,9 @@ otsdb_status partials_locked(otsdb_ctx* c, const otsdb_query_spec* spec,
     rc = run_pipeline(c, spec, B, b->group_members, goff, P, W, 1,
                       (Packed*)partials, emit, nullptr, nullptr,
                       (const Packed*)init, init_emit);
-    if (!rc) {
-      HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
-                             hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      const int err = (int)(c->h_small[0] & 0xFFFFFFFF);
-      if (err & ERR_RATE_TS)
-        rc = fail(OTSDB_E_ILLEGAL_STATE,
-                  "Next timestamp is supposed to be strictly greater");
-    }
+    int err = 0;
+    if (!rc) rc = read_err(c, &err);
+    if (!rc && (err & ERR_RATE_TS)) rc = rate_ts_error();
   }
   return rc;
 }
@@ -4323,20 +4280,17 @@ otsdb_status partials_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
                            uint8_t* emit, void* hip_stream) {
   if (!c || !spec || !b || !partials || !emit || (!init != !init_emit))
     return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  StreamBinding bind(c, hip_stream);
-  std::vector<int64_t> goff;
-  otsdb_status rc = read_goff(c, b, true, goff);
-  if (!rc) rc = partials_locked(c, spec, b, goff, init, init_emit, partials, emit);
-  return rc;
+  DeviceCall dc(c, b, hip_stream);
+  return dc.rc ? dc.rc
+               : partials_locked(c, spec, b, dc.goff, init, init_emit, partials,
+                                 emit);
 }
 
 // the multi_request checks of the entries that exchange partials: the
 // selections take the otsdb_sel_* protocol
 otsdb_status check_multi_partials(const otsdb_query_spec* spec,
-                                  const MultiReq& q) {
-  const otsdb_status rc = check_multi(spec, q);
+                                  const Req& q) {
+  const otsdb_status rc = check_req(spec, q);
   if (rc) return rc;
   for (int i = 0; i < q.n; ++i)
     if (is_selection(q.aggs[i]))
@@ -4355,30 +4309,26 @@ otsdb_status otsdb_agg_partials_multi_device(
     otsdb_partial* partials, uint8_t* emit, void* hip_stream) {
   if (!c || !spec || !b || !partials || !emit)
     return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  const MultiReq q{n_out, agg_ids, interps, nullptr};
+  const Req q{n_out, nullptr, agg_ids, interps, nullptr};
   otsdb_status rc = check_multi_partials(spec, q);
   if (rc) return rc;
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  StreamBinding bind(c, hip_stream);
-  std::vector<int64_t> goff;
-  rc = read_goff(c, b, true, goff);
-  if (rc) return rc;
-  const otsdb_query_spec s0 = multi_spec(spec, q, 0);
+  DeviceCall dc(c, b, hip_stream);
+  if (dc.rc) return dc.rc;
+  std::vector<int64_t>& goff = dc.goff;
+  const otsdb_query_spec s0 = req_spec(spec, q, 0);
   Params P;
   rc = partials_grid(c, &s0, b, &P);
   if (rc) return rc;
   c->multi_failed = -1;
-  c->n_multi_ds = c->n_multi_group = c->n_multi_kt = c->n_multi_tf = 0;
+  multi_counters(c, 0, 0);
   const int64_t G = (int64_t)goff.size() - 1;
   const size_t GB = (size_t)G * P.nb;
   // (a misaligned batch: the single path reports it)
-  if (((((uintptr_t)b->ts_ms) | ((uintptr_t)b->val)) & 15) ||
-      !multi_shares_rows(spec, q, P, b->n_series, goff)) {
+  if (misaligned(b) || !multi_shares_rows(spec, q, P, b->n_series, goff)) {
     // the outputs one after another through the single entry's path: every
     // one writes the same emit mask
     for (int i = 0; i < q.n; ++i) {
-      const otsdb_query_spec si = multi_spec(spec, q, i);
+      const otsdb_query_spec si = req_spec(spec, q, i);
       rc = partials_locked(c, &si, b, goff, nullptr, nullptr,
                            partials + (size_t)i * GB, emit);
       if (rc) {
@@ -4396,20 +4346,15 @@ otsdb_status otsdb_agg_partials_multi_device(
       return fail(OTSDB_E_UNSUPPORTED,
                   "exact-order dev across ranks: hand the chains on "
                   "(otsdb_agg_partials_chained_device)");
-  BatchDev B{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
-             b->series_float};
+  const BatchDev B = batch_dev(b);
   MultiState M;
   rc = multi_build(c, &s0, q, B, b->group_members, goff, P, nullptr, nullptr, M,
                    /*partial=*/true);
   if (!rc) rc = multi_partials(c, M, (Packed*)partials, emit);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
-                         hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if ((int)(c->h_small[0] & 0xFFFFFFFF) & ERR_RATE_TS)
-    return fail(OTSDB_E_ILLEGAL_STATE,
-                "Next timestamp is supposed to be strictly greater");
-  return OTSDB_OK;
+  int err;
+  if ((rc = read_err(c, &err))) return rc;
+  return (err & ERR_RATE_TS) ? rate_ts_error() : OTSDB_OK;
 }
 
 otsdb_status otsdb_agg_finalize_multi_device(
@@ -4418,7 +4363,7 @@ otsdb_status otsdb_agg_finalize_multi_device(
     int64_t n_buckets, int32_t n_ranks, const otsdb_partial* partials,
     const uint8_t* emit, otsdb_result* outs, void* hip_stream) {
   if (!c || !spec || !outs) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  const MultiReq q{n_out, agg_ids, interps, outs};
+  const Req q{n_out, nullptr, agg_ids, interps, outs};
   otsdb_status rc = check_multi_partials(spec, q);
   if (rc) return rc;
   if (n_groups < 0 || n_ranks < 1)
@@ -4427,7 +4372,7 @@ otsdb_status otsdb_agg_finalize_multi_device(
   CtxLock lk(c);
   HIP_TRY(hipSetDevice(c->device));
   StreamBinding bind(c, hip_stream);
-  const otsdb_query_spec s0 = multi_spec(spec, q, 0);
+  const otsdb_query_spec s0 = req_spec(spec, q, 0);
   Params P;
   rc = make_params(&s0, &P, c);
   if (!rc && P.nb != n_buckets)
@@ -4515,19 +4460,19 @@ otsdb_status otsdb_agg_finalize_device(otsdb_ctx* c,
               (long long)n_buckets, (long long)P.nb);
   if (!rc) {
     const int64_t G = n_groups, GB = G * P.nb;
+    double* ov;
+    uint8_t* oe;
+    int64_t* cnt;
     auto carve = [&](char* base) {
       Carve cv{base};
-      double* v = cv.take<double>(GB + 1);
-      uint8_t* e = cv.take<uint8_t>(GB + 1);
-      int64_t* cnt = cv.take<int64_t>(G + 1);
-      return std::make_tuple(cv.off + 256, v, e, cnt);
+      ov = cv.take<double>(GB + 1);
+      oe = cv.take<uint8_t>(GB + 1);
+      cnt = cv.take<int64_t>(G + 1);
+      return cv.off + 256;
     };
-    rc = ensure(&c->ws, &c->ws_cap, std::get<0>(carve(nullptr)));
+    rc = ensure(&c->ws, &c->ws_cap, carve(nullptr));
     if (!rc) {
-      auto t = carve((char*)c->ws);
-      double* ov = std::get<1>(t);
-      uint8_t* oe = std::get<2>(t);
-      int64_t* cnt = std::get<3>(t);
+      carve((char*)c->ws);
       hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream);
       bool ok = true;
       if (GB > 0)
@@ -4553,12 +4498,9 @@ otsdb_status otsdb_sel_prepare_device(otsdb_ctx* c, const otsdb_query_spec* spec
                                       void* hip_stream) {
   if (!c || !spec || !b || !counts || !emit || !krange)
     return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  c->sel.active = false;
-  StreamBinding bind(c, hip_stream);
-  std::vector<int64_t> goff;
-  otsdb_status rc = read_goff(c, b, true, goff);
+  DeviceCall dc(c, b, hip_stream);  // (the lock ends an earlier session)
+  std::vector<int64_t>& goff = dc.goff;
+  otsdb_status rc = dc.rc;
   Params P;
   if (!rc) rc = check_spec(spec);
   if (!rc && !is_selection(spec->agg_id))
@@ -4569,8 +4511,7 @@ otsdb_status otsdb_sel_prepare_device(otsdb_ctx* c, const otsdb_query_spec* spec
   if (!rc && !P.run_all && !P.fill && (double)b->n_series * (double)P.nb > 4.0e9)
     rc = fail(OTSDB_E_UNSUPPORTED, "grid trimming is not supported across ranks");
   if (!rc) {
-    BatchDev B{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
-               b->series_float};
+    const BatchDev B = batch_dev(b);
     Work W;
     rc = run_pipeline(c, spec, B, b->group_members, goff, P, W, 2, nullptr,
                       nullptr);
@@ -4594,12 +4535,9 @@ otsdb_status otsdb_sel_prepare_device(otsdb_ctx* c, const otsdb_query_spec* spec
     }
     if (!rc) {
       HIP_TRY(hipMemsetAsync((char*)c->d_err + 128, 0, 32, c->stream));
-      HIP_TRY(hipMemcpyAsync(&c->h_small[0], c->d_err, sizeof(int),
-                             hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if ((int)(c->h_small[0] & 0xFFFFFFFF) & ERR_RATE_TS)
-        rc = fail(OTSDB_E_ILLEGAL_STATE,
-                  "Next timestamp is supposed to be strictly greater");
+      int err = 0;
+      rc = read_err(c, &err);
+      if (!rc && (err & ERR_RATE_TS)) rc = rate_ts_error();
     }
     if (!rc) {
       auto& S = c->sel;
@@ -4935,13 +4873,10 @@ otsdb_status otsdb_agg_run_raw_device(otsdb_ctx* c, const otsdb_query_spec* spec
                                       void* hip_stream) {
   if (!c || !spec || !raw || !b || !out)
     return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  StreamBinding bind(c, hip_stream);
-  std::vector<int64_t> goff;
-  otsdb_status rc = read_goff(c, b, true, goff);
+  DeviceCall dc(c, b, hip_stream);
+  otsdb_status rc = dc.rc;
   if (!rc) rc = check_spec(spec);
-  if (!rc) rc = run_raw_impl(c, spec, raw, fix_duplicates != 0, b, out, goff);
+  if (!rc) rc = run_raw_impl(c, spec, raw, fix_duplicates != 0, b, out, dc.goff);
   return rc;
 }
 

@@ -154,6 +154,27 @@ def panel_args(queries):
     return n, ds, ids, it
 
 
+def _host_results(n, G, cap):
+    """n host results of capacity `cap` for G groups: the abi.Result array
+    and a function that slices them into one list of DataPoints (one per
+    group) per result, after the call filled them."""
+    offs = np.zeros((n, G + 1), np.int64)
+    ts = np.zeros((n, cap), np.int64)
+    bits = np.zeros((n, cap), np.int64)
+    isint = np.zeros((n, cap), np.uint8)
+    rs = (abi.Result * n)()
+    for i in range(n):
+        rs[i] = abi.Result(cap, offs[i].ctypes.data, ts[i].ctypes.data,
+                           bits[i].ctypes.data, isint[i].ctypes.data)
+
+    def points():
+        return [[DataPoints(ts[i, offs[i, g]:offs[i, g + 1]],
+                            bits[i, offs[i, g]:offs[i, g + 1]],
+                            isint[i, offs[i, g]:offs[i, g + 1]])
+                 for g in range(G)] for i in range(n)]
+    return rs, points
+
+
 class Engine:
     """One context per GPU (one process per GPU)."""
 
@@ -163,12 +184,16 @@ class Engine:
         self._check(self.lib.otsdb_ctx_create(int(device), C.byref(self.ctx)))
         self.device = device
 
+    def _counters(self, n):
+        out = (C.c_int64 * n)()
+        self._check(self.lib.otsdb_ctx_counters(self.ctx, out, n))
+        return out
+
     def counters(self):
         """otsdb_ctx_counters: {cells folds run uniform / general, uniform
         folds re-run with the general kernel; the last otsdb_sel_* session's
         passes over the local keys and histogram passes}."""
-        out = (C.c_int64 * 5)()
-        self._check(self.lib.otsdb_ctx_counters(self.ctx, out, 5))
+        out = self._counters(5)
         return dict(cells_uniform=out[0], cells_general=out[1],
                     cells_uniform_miss=out[2], sel_key_reads=out[3],
                     sel_passes=out[4])
@@ -179,8 +204,7 @@ class Engine:
         row matrix, key transposes, transform passes (one per interpolation
         class).  A call that cannot share the rows runs its outputs as single
         queries: downsample and group passes then count those."""
-        out = (C.c_int64 * 9)()
-        self._check(self.lib.otsdb_ctx_counters(self.ctx, out, 9))
+        out = self._counters(9)
         return dict(downsample_passes=out[5], group_passes=out[6],
                     key_transposes=out[7], transform_passes=out[8])
 
@@ -188,16 +212,13 @@ class Engine:
         """Of the last panel call (otsdb_ctx_counters [10..11]): passes over
         the point stream (one for all envelope functions that share a pass,
         one per multi call otherwise) and row matrices built."""
-        out = (C.c_int64 * 12)()
-        self._check(self.lib.otsdb_ctx_counters(self.ctx, out, 12))
+        out = self._counters(12)
         return dict(point_stream_passes=out[10], row_matrices=out[11])
 
     def sel_sessions(self):
         """otsdb_ctx_counters [9]: otsdb_sel_* sessions prepared since the
         context was created (a retargeted session counts once)."""
-        out = (C.c_int64 * 10)()
-        self._check(self.lib.otsdb_ctx_counters(self.ctx, out, 10))
-        return int(out[9])
+        return int(self._counters(10)[9])
 
     def close(self):
         if self.ctx:
@@ -255,24 +276,13 @@ class Engine:
         per aggregator, each what run() gives for that aggregator."""
         n, ids, it = multi_args(aggs, interps)
         sz = self.plan_multi(spec, ids, batch, it)
-        cap = max(1, int(sz.max_out_points))
-        G = batch.n_groups
-        offs = np.zeros((n, G + 1), np.int64)
-        ts = np.zeros((n, cap), np.int64)
-        bits = np.zeros((n, cap), np.int64)
-        isint = np.zeros((n, cap), np.uint8)
-        rs = (abi.Result * n)()
-        for i in range(n):
-            rs[i] = abi.Result(cap, offs[i].ctypes.data, ts[i].ctypes.data,
-                               bits[i].ctypes.data, isint[i].ctypes.data)
+        rs, points = _host_results(n, batch.n_groups,
+                                   max(1, int(sz.max_out_points)))
         b = batch.as_abi()
         self._check(self.lib.otsdb_agg_run_multi(
             self.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
             C.byref(b), rs))
-        return [[DataPoints(ts[i, offs[i, g]:offs[i, g + 1]],
-                            bits[i, offs[i, g]:offs[i, g + 1]],
-                            isint[i, offs[i, g]:offs[i, g + 1]])
-                 for g in range(G)] for i in range(n)]
+        return points()
 
     def plan_panel(self, spec, queries, batch):
         n, ds, ids, it = panel_args(queries)
@@ -289,29 +299,16 @@ class Engine:
         function and interpolation are ignored.  Returns one list of
         DataPoints (one per group) per query, each what run() gives for that
         query."""
+        queries = [tuple(q) for q in queries]
         n, ds, ids, it = panel_args(queries)
-        sz = abi.Sizes()
-        self._check(self.lib.otsdb_agg_plan_panel(
-            self.ctx, C.byref(spec), n, ds.ctypes.data, ids.ctypes.data,
-            it.ctypes.data, C.byref(batch.as_abi()), C.byref(sz)))
-        cap = max(1, int(sz.max_out_points))
-        G = batch.n_groups
-        offs = np.zeros((n, G + 1), np.int64)
-        ts = np.zeros((n, cap), np.int64)
-        bits = np.zeros((n, cap), np.int64)
-        isint = np.zeros((n, cap), np.uint8)
-        rs = (abi.Result * n)()
-        for i in range(n):
-            rs[i] = abi.Result(cap, offs[i].ctypes.data, ts[i].ctypes.data,
-                               bits[i].ctypes.data, isint[i].ctypes.data)
+        sz = self.plan_panel(spec, queries, batch)
+        rs, points = _host_results(n, batch.n_groups,
+                                   max(1, int(sz.max_out_points)))
         b = batch.as_abi()
         self._check(self.lib.otsdb_agg_run_panel(
             self.ctx, C.byref(spec), n, ds.ctypes.data, ids.ctypes.data,
             it.ctypes.data, C.byref(b), rs))
-        return [[DataPoints(ts[i, offs[i, g]:offs[i, g + 1]],
-                            bits[i, offs[i, g]:offs[i, g + 1]],
-                            isint[i, offs[i, g]:offs[i, g + 1]])
-                 for g in range(G)] for i in range(n)]
+        return points()
 
 
 class DeviceBatch:
@@ -414,6 +411,24 @@ _BATCH_TENSORS = ("offsets", "ts", "val", "is_float", "series_float",
 _RESULT_TENSORS = ("offsets", "ts", "val", "is_int")
 
 
+def _stream(stream):
+    return None if stream is None else C.c_void_p(stream)
+
+
+def _result_array(dresults, n, what, cached=True):
+    """The abi.Result array of n DeviceResults, one per output (`what`: what
+    the outputs are, for the message); cached: their structs through
+    _abi_cached."""
+    if len(dresults) != n:
+        raise IllegalArgumentException(
+            "%d results for %d %s" % (len(dresults), n, what))
+    rs = (abi.Result * n)()
+    for i, r in enumerate(dresults):
+        rs[i] = (_abi_cached(r, _RESULT_TENSORS, r.as_abi, r.cap) if cached
+                 else r.as_abi())
+    return rs
+
+
 def run_device(engine, spec, dbatch, dresult, stream=None):
     """Device-resident path: no host copies of points in or out."""
     b = _abi_cached(dbatch, _BATCH_TENSORS, dbatch.as_abi,
@@ -430,17 +445,12 @@ def run_multi_device(engine, spec, aggs, dbatch, dresults, stream=None,
     takes what run_device gives for aggs[i]; the point stream is downsampled
     once for all of them."""
     n, ids, it = multi_args(aggs, interps)
-    if len(dresults) != n:
-        raise IllegalArgumentException(
-            "%d results for %d aggregators" % (len(dresults), n))
+    rs = _result_array(dresults, n, "aggregators")
     b = _abi_cached(dbatch, _BATCH_TENSORS, dbatch.as_abi,
                     dbatch.group_offsets._version)
-    rs = (abi.Result * n)()
-    for i, r in enumerate(dresults):
-        rs[i] = _abi_cached(r, _RESULT_TENSORS, r.as_abi, r.cap)
     engine._check(engine.lib.otsdb_agg_run_multi_device(
         engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
-        C.byref(b), rs, None if stream is None else C.c_void_p(stream)))
+        C.byref(b), rs, _stream(stream)))
 
 
 def run_panel_device(engine, spec, queries, dbatch, dresults, stream=None):
@@ -449,18 +459,12 @@ def run_panel_device(engine, spec, queries, dbatch, dresults, stream=None):
     [, interpolation]); the envelope functions share one pass over the point
     stream."""
     n, ds, ids, it = panel_args(queries)
-    if len(dresults) != n:
-        raise IllegalArgumentException(
-            "%d results for %d queries" % (len(dresults), n))
+    rs = _result_array(dresults, n, "queries")
     b = _abi_cached(dbatch, _BATCH_TENSORS, dbatch.as_abi,
                     dbatch.group_offsets._version)
-    rs = (abi.Result * n)()
-    for i, r in enumerate(dresults):
-        rs[i] = _abi_cached(r, _RESULT_TENSORS, r.as_abi, r.cap)
     engine._check(engine.lib.otsdb_agg_run_panel_device(
         engine.ctx, C.byref(spec), n, ds.ctypes.data, ids.ctypes.data,
-        it.ctypes.data, C.byref(b), rs,
-        None if stream is None else C.c_void_p(stream)))
+        it.ctypes.data, C.byref(b), rs, _stream(stream)))
 
 
 def partials_multi_device(engine, spec, aggs, dbatch, partials, emit,
@@ -474,8 +478,7 @@ def partials_multi_device(engine, spec, aggs, dbatch, partials, emit,
                     dbatch.group_offsets._version)
     engine._check(engine.lib.otsdb_agg_partials_multi_device(
         engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
-        C.byref(b), partials.data_ptr(), emit.data_ptr(),
-        None if stream is None else C.c_void_p(stream)))
+        C.byref(b), partials.data_ptr(), emit.data_ptr(), _stream(stream)))
 
 
 def finalize_multi_device(engine, spec, aggs, n_groups, n_buckets, n_ranks,
@@ -484,13 +487,8 @@ def finalize_multi_device(engine, spec, aggs, n_groups, n_buckets, n_ranks,
     n_buckets, 4] and emit [n_ranks, G * n_buckets] merged in rank order,
     output i into dresults[i]."""
     n, ids, it = multi_args(aggs, interps)
-    if len(dresults) != n:
-        raise IllegalArgumentException(
-            "%d results for %d aggregators" % (len(dresults), n))
-    rs = (abi.Result * n)()
-    for i, r in enumerate(dresults):
-        rs[i] = r.as_abi()
+    rs = _result_array(dresults, n, "aggregators", cached=False)
     engine._check(engine.lib.otsdb_agg_finalize_multi_device(
         engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
         int(n_groups), int(n_buckets), int(n_ranks), partials.data_ptr(),
-        emit.data_ptr(), rs, None if stream is None else C.c_void_p(stream)))
+        emit.data_ptr(), rs, _stream(stream)))

@@ -247,17 +247,24 @@ def decode_cells_device(engine, cells, capacity=None, out=None):
     return offsets, ts[:capacity], val[:capacity], isf[:capacity]
 
 
+def _cells_batch(cells, groups):
+    """The points-less otsdb_batch of a cells query: the series count of the
+    cells, the group arrays of `groups` (a DeviceBatch-like object)."""
+    b = abi.Batch()
+    b.n_series = cells.n_series
+    b.n_points = 0
+    b.n_groups = groups.n_groups
+    b.group_offsets = groups.group_offsets.data_ptr()
+    b.group_members = groups.group_members.data_ptr()
+    return b
+
+
 def run_cells_device(engine, spec, cells, db_groups, result):
     """otsdb_agg_run_cells_device: the query straight from compacted columns
     (decode fused into the downsample).  db_groups: a DeviceBatch-like object
     supplying n_series and the group arrays."""
     import ctypes as C
-    b = abi.Batch()
-    b.n_series = cells.n_series
-    b.n_points = 0
-    b.n_groups = db_groups.n_groups
-    b.group_offsets = db_groups.group_offsets.data_ptr()
-    b.group_members = db_groups.group_members.data_ptr()
+    b = _cells_batch(cells, db_groups)
     c = cells.as_abi()
     r = result.as_abi()
     engine._check(engine.lib.otsdb_agg_run_cells_device(
@@ -269,21 +276,11 @@ def run_cells_multi_device(engine, spec, aggs, cells, db_groups, results,
     """otsdb_agg_run_cells_multi_device: several aggregators over one decode
     + downsample of the compacted columns; results[i] takes aggs[i]'s."""
     import ctypes as C
-    from .engine import multi_args
+    from .engine import _result_array, multi_args
     n, ids, it = multi_args(aggs, interps)
-    if len(results) != n:
-        raise core.IllegalArgumentException(
-            "%d results for %d aggregators" % (len(results), n))
-    b = abi.Batch()
-    b.n_series = cells.n_series
-    b.n_points = 0
-    b.n_groups = db_groups.n_groups
-    b.group_offsets = db_groups.group_offsets.data_ptr()
-    b.group_members = db_groups.group_members.data_ptr()
+    rs = _result_array(results, n, "aggregators", cached=False)
+    b = _cells_batch(cells, db_groups)
     c = cells.as_abi()
-    rs = (abi.Result * n)()
-    for i, r in enumerate(results):
-        rs[i] = r.as_abi()
     engine._check(engine.lib.otsdb_agg_run_cells_multi_device(
         engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
         C.byref(c), C.byref(b), rs, None))
@@ -297,22 +294,11 @@ def run_cells_panel_device(engine, spec, queries, dcells, dbatch, dresults,
     envelope functions share one decode + downsample of the columns.
     dbatch: a DeviceBatch-like object supplying the group arrays."""
     import ctypes as C
-    from .engine import panel_args
+    from .engine import _result_array, _stream, panel_args
     n, ds, ids, it = panel_args(queries)
-    if len(dresults) != n:
-        raise core.IllegalArgumentException(
-            "%d results for %d queries" % (len(dresults), n))
-    b = abi.Batch()
-    b.n_series = dcells.n_series
-    b.n_points = 0
-    b.n_groups = dbatch.n_groups
-    b.group_offsets = dbatch.group_offsets.data_ptr()
-    b.group_members = dbatch.group_members.data_ptr()
+    rs = _result_array(dresults, n, "queries", cached=False)
+    b = _cells_batch(dcells, dbatch)
     c = dcells.as_abi()
-    rs = (abi.Result * n)()
-    for i, r in enumerate(dresults):
-        rs[i] = r.as_abi()
     engine._check(engine.lib.otsdb_agg_run_cells_panel_device(
         engine.ctx, C.byref(spec), n, ds.ctypes.data, ids.ctypes.data,
-        it.ctypes.data, C.byref(c), C.byref(b), rs,
-        None if stream is None else C.c_void_p(stream)))
+        it.ctypes.data, C.byref(c), C.byref(b), rs, _stream(stream)))
