@@ -120,6 +120,7 @@ typedef enum {
 /* Query spec: one per query (all groups share it).                          */
 /* ------------------------------------------------------------------------ */
 #define OTSDB_SPEC_EXACT_ORDER 1
+#define OTSDB_SPEC_MULTI_FOLD 2 /* otsdb_agg_run_multi*: see there */
 typedef struct {
   /* AggregationIterator window, ms, inclusive on both ends
    * (SpanGroup ctor normalises the scan bounds to ms, SpanGroup.java:267-270;
@@ -300,6 +301,22 @@ otsdb_status otsdb_agg_run_device(otsdb_ctx* ctx, const otsdb_query_spec* spec,
  * single query.  Queries that cannot share the rows (raw group-by,
  * per-series calendar anchors, OTSDB_SPEC_EXACT_ORDER dev past the row
  * budget) run their outputs one after another: same results, nothing shared.
+ * spec->flags & OTSDB_SPEC_MULTI_FOLD (opt-in): a call whose outputs are all
+ * of sum / zimsum / pfsum / avg / count / min / mimmin / max / mimmax and
+ * share ONE interpolation (the same default or override for every output, or
+ * any fill policy), on a query the single path runs through the ordered fold
+ * (downsampled, no rate, no "all", no median / percentile downsampling),
+ * through the columnar entries (otsdb_agg_run_multi, _run_multi_device and a
+ * panel call of one distinct downsampling function), takes ONE ordered fold
+ * over a combined {sum, count, min, max} state: no row matrix, no transform
+ * and no group pass (otsdb_ctx_counters [5..8] = 1, 0, 0, 0 and [12] = 1).
+ * Output i is reduced over the single query's tiles in the single query's
+ * order: bit for bit otsdb_agg_run's for an order-free downsampling function
+ * (min, max, count, first, last ...) and on grids of up to 128 buckets,
+ * within 1e-12 of it otherwise (sum / avg downsampling on wider grids: the
+ * fold's windows differ).  Every other request ignores the
+ * flag and runs exactly as without it ([12] = 0); the cells and partials
+ * entries never read it.
  * plan_multi: max_out_points bounds EACH output, workspace_bytes the call.  */
 #define OTSDB_MULTI_MAX 32
 otsdb_status otsdb_agg_plan_multi(otsdb_ctx* ctx, const otsdb_query_spec* spec,
@@ -750,7 +767,9 @@ otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
  * interpolation class).  out[9]: otsdb_sel_* sessions prepared since the
  * context was created (otsdb_sel_retarget prepares none).  Of the last
  * otsdb_agg_run_panel* call: out[10] passes over the point stream, out[11]
- * row matrices built (the multi calls inside it still maintain [5..8]).    */
+ * row matrices built (the multi calls inside it still maintain [5..8]).
+ * out[12]: multi-aggregator folds launched by the last otsdb_agg_*_multi*
+ * call (OTSDB_SPEC_MULTI_FOLD on an eligible request: 1, else 0).            */
 otsdb_status otsdb_ctx_counters(otsdb_ctx* ctx, int64_t* out, int n);
 /* Test hook: the one-pass compaction's epoch (1 .. 2^24 - 1, forward only)
  * the context's next call increments, so tests can drive it to its wrap.  */

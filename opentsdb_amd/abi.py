@@ -133,6 +133,7 @@ class GenSpec(C.Structure):
 
 
 SPEC_EXACT_ORDER = 1  # otsdb_query_spec.flags
+SPEC_MULTI_FOLD = 2   # ... a multi call may take the multi-aggregator fold
 
 
 EXPORTS = [

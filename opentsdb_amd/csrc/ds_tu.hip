@@ -50,6 +50,8 @@
 #include "fold.hip"
 #if OTSDB_DS_PART == 1
 #include "cellfold.hip"
+#else
+#include "foldmulti.hip"
 #endif
 
 namespace otsdb {
@@ -207,6 +209,26 @@ bool launch_ds(DsKernel k, const DsLaunch& a) {
                            a.always_partial, a.cf);
         OTSDB_DBG(a.st, "k_fold");
       });
+    case DS_FOLD_MULTI: {
+      // as DS_FOLD: the contexts only while the workgroup stays 4 to a CU
+      // (full-width windows of 1,024 envelope states leave no room)
+      Params P = a.P;
+      size_t lds = fold_lds_bytes<MEnv>(P);
+      if (P.fold_ctx > 0 && lds + (size_t)P.fold_ctx * sizeof(FoldMember) <=
+                                kFoldDynBudget)
+        lds += (size_t)P.fold_ctx * sizeof(FoldMember);
+      else
+        P.fold_ctx = 0;
+      hipLaunchKernelGGL((k_fold_multi<M, 8>),
+                         dim3((unsigned)(a.n_tiles * a.NW)), dim3(FOLD_THREADS),
+                         (unsigned)lds, a.st, P, a.B, a.SM, a.n_tiles, a.tg,
+                         a.tm0, a.tm1, a.single, a.members, a.wc, a.NW,
+                         a.tile_emit, a.err, *a.fm);
+      OTSDB_DBG(a.st, "k_fold_multi");
+      return true;
+    }
+    default:
+      break;
   }
   return false;
 }

@@ -320,6 +320,9 @@ struct otsdb_ctx {
   // the point stream, group-stage passes over a row matrix, key transposes,
   // transform passes
   int64_t n_multi_ds = 0, n_multi_group = 0, n_multi_kt = 0, n_multi_tf = 0;
+  // otsdb_ctx_counters [12], of the last multi call: k_fold_multi launches
+  // (OTSDB_SPEC_MULTI_FOLD on an eligible request: 1, else 0)
+  int64_t n_multi_fold = 0;
   // otsdb_ctx_counters [10..11], of the last panel call: passes over the
   // point stream, row matrices built
   int64_t n_panel_passes = 0, n_panel_mats = 0;
@@ -423,6 +426,7 @@ void multi_counters(otsdb_ctx* c, int64_t ds, int64_t group) {
   c->n_multi_ds = ds;
   c->n_multi_group = group;
   c->n_multi_kt = c->n_multi_tf = 0;
+  c->n_multi_fold = 0;
 }
 
 // --------------------------------------------------------------- planning
@@ -2622,10 +2626,198 @@ otsdb_status multi_sequential(otsdb_ctx* c, const otsdb_query_spec* spec,
   return OTSDB_OK;
 }
 
+// ---- OTSDB_SPEC_MULTI_FOLD: every output from one ordered fold ------------
+// the component of the envelope state (menv.h) an aggregator finishes from,
+// -1: not in the envelope set
+int fold_multi_kind(int agg) {
+  switch (agg) {
+    case OTSDB_AGG_SUM:
+    case OTSDB_AGG_PFSUM:
+    case OTSDB_AGG_ZIMSUM: return FM_SUM;
+    case OTSDB_AGG_AVG: return FM_AVG;
+    case OTSDB_AGG_COUNT: return FM_CNT;
+    case OTSDB_AGG_MIN:
+    case OTSDB_AGG_MIMMIN: return FM_MIN;
+    case OTSDB_AGG_MAX:
+    case OTSDB_AGG_MIMMAX: return FM_MAX;
+    default: return -1;
+  }
+}
+
+// Whether a multi call that can share its rows (multi_shares_rows) takes the
+// fold instead: the caller asked for it, the single queries would fold
+// (fold_path), every aggregator is a component of the envelope state and all
+// outputs contribute through one interpolation class (the fold bakes it into
+// the contributions as it pushes them).
+bool multi_folds(const otsdb_query_spec* s0, const Req& q, const Params& P) {
+  if (!(s0->flags & OTSDB_SPEC_MULTI_FOLD) || q.n < 2) return false;
+  for (int i = 0; i < q.n; ++i) {
+    const otsdb_query_spec si = req_spec(s0, q, i);
+    if (fold_multi_kind(si.agg_id) < 0 || !fold_path(&si, P, 0)) return false;
+  }
+  int cls[OTSDB_MULTI_MAX], ci[OTSDB_MULTI_MAX];
+  return multi_classes(q, P, cls, ci) == 1;
+}
+
+// The folded multi call: run_pipeline's fold branch with k_fold_multi in
+// k_fold's place — the single fold's tiles (groups up to kFoldChunk members
+// whole, larger ones in tiles of kFoldChunkLarge), windows of
+// fold_wb<MEnv>() buckets narrowed by the single fold's rule, the same prep
+// kernels — then k_combine<M> per output over the tiles of larger groups and
+// the compaction of every output.  No row matrix, no transform, no group
+// pass.
+otsdb_status multi_fold(otsdb_ctx* c, const otsdb_query_spec* s0,
+                        const Req& q, const BatchDev& B,
+                        const int64_t* d_members, std::vector<int64_t>& goff,
+                        const Params& P0) {
+  hipStream_t st = c->stream;
+  otsdb_status rc = multi_buffers(c);
+  if (rc) return rc;
+  Params P = P0;
+  const int64_t S = B.S, NB = P.nb;
+  const int64_t G = (int64_t)goff.size() - 1;
+  int cls[OTSDB_MULTI_MAX], ci[OTSDB_MULTI_MAX];
+  multi_classes(q, P, cls, ci);
+  P.interp = ci[0];
+  P.sentinel = 0;
+  rc = build_tiles(c, goff, false, kFoldChunkLarge, kFoldChunk);
+  if (rc) return rc;
+  const Tiles T = tiles_of(c, G);
+  int64_t WB = fold_wb<MEnv>();
+  int64_t NW = (NB + WB - 1) / WB;
+  P.fold_wb = 0;
+  P.fold_ctx = 0;
+  // the largest tile's member contexts preloaded (ds_tu.hip drops them when
+  // the LDS would cost occupancy), as for the single fold
+  bool empty_group = false;
+  int64_t tile_max = 0;
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t k = goff[g + 1] - goff[g];
+    empty_group |= k == 0;
+    tile_max = std::max(tile_max,
+                        k <= kFoldChunk ? k : std::min(k, kFoldChunkLarge));
+  }
+  if (OTSDB_FOLD_CTX && tile_max > 0 && tile_max <= 64)
+    P.fold_ctx = (int32_t)tile_max;
+  // few tiles: narrower windows, the single fold's rule over this state's cap
+  if (T.T > 0 && NB > kFoldMinWindow && T.T * NW < kFoldMinBlocks) {
+    const int64_t want = (kFoldMinBlocks + T.T - 1) / T.T;  // windows
+    int64_t wb = (NB + want - 1) / want;
+    wb = (wb + 63) / 64 * 64;
+    if (wb < kFoldMinWindow) wb = kFoldMinWindow;
+    if (wb < WB) {
+      WB = wb;
+      NW = (NB + WB - 1) / WB;
+      P.fold_wb = (int32_t)WB;
+    }
+  }
+  // which partials the tiles of larger groups leave
+  FoldMultiArgs FM{};
+  FM.n_out = q.n;
+  bool need_sn = false, need_mn = false, need_mx = false;
+  for (int i = 0; i < q.n; ++i) {
+    const int k = FM.kind[i] = fold_multi_kind(q.aggs[i]);
+    need_sn |= k == FM_SUM || k == FM_AVG || k == FM_CNT;
+    need_mn |= k == FM_MIN;
+    need_mx |= k == FM_MAX;
+  }
+  const bool two_level = two_level_combine(T.max_chunks, T.MG, NB);
+  Work W;
+  WinCtx* wc = nullptr;
+  double* out_val[OTSDB_MULTI_MAX];
+  uint8_t* out_emit[OTSDB_MULTI_MAX];
+  auto carve = [&](char* base) {
+    Carve cv{base};
+    carve_series(cv, W, S);
+    const size_t tp = T.MG > 0 ? (size_t)T.T * NB : 0;
+    FM.part_sn = need_sn && tp ? cv.take<Packed>(tp) : nullptr;
+    FM.part_mn = need_mn && tp ? cv.take<Packed>(tp) : nullptr;
+    FM.part_mx = need_mx && tp ? cv.take<Packed>(tp) : nullptr;
+    W.tile_emit = cv.take<uint8_t>((size_t)T.T * NB);
+    for (int i = 0; i < q.n; ++i) {
+      out_val[i] = cv.take<double>((size_t)G * NB);
+      out_emit[i] = cv.take<uint8_t>((size_t)G * NB);
+    }
+    if (NW > 1) wc = cv.take<WinCtx>((size_t)S * (NW - 1));
+    if (two_level) carve_combine(cv, W, T.MG, NB);
+    return cv.off + 256;
+  };
+  rc = ensure(&c->ws, &c->ws_cap, carve(nullptr));
+  if (rc) return rc;
+  carve((char*)c->ws);
+  W.R = Rows{nullptr, nullptr};
+  W.partial = nullptr;
+  W.out_val = nullptr;
+  W.out_emit = nullptr;
+  W.counts = nullptr;
+  // every output its own error word; prep and the fold's watchdog report
+  // into the context's (folded into every output's status at the end)
+  HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(int), st));
+  HIP_TRY(hipMemsetAsync(c->d_merr, 0, OTSDB_MULTI_MAX * sizeof(int), st));
+  c->clean_entry = false;
+  // the fold / k_combine write every emit flag of a group with members
+  if (empty_group && G * NB > 0)
+    for (int i = 0; i < q.n; ++i)
+      HIP_TRY(hipMemsetAsync(out_emit[i], 0, (size_t)G * NB, st));
+  for (int i = 0; i < q.n; ++i)
+    FM.out[i] = FoldMultiOut{out_val[i], out_emit[i], c->d_merr + q.e0 + i};
+  multi_counters(c, 0, 0);
+  // (multi_shares_rows: series, members and buckets exist, so every dense
+  // output below is written by the fold or by k_combine)
+  if (S > 0 && NB > 0 && T.T > 0) {
+    DsLaunch a = ds_args(c, P, B, W);
+    const bool ok = with_monoid(s0->ds_agg_id, [&](auto tag) {
+      using M = decltype(tag);
+      {
+        StageTimer tm(c, 3);
+        a.wc = wc;
+        a.NW = NW;
+        a.WB = WB;
+        if (NW > 1 && S * (NW - 1) <= prep_fold_max()) {
+          launch_ds<M>(DS_PREP_FOLD, a);
+        } else {
+          launch_ds<M>(DS_PREP, a);
+          if (NW > 1) launch_ds<M>(DS_FOLD_PREP, a);
+        }
+      }
+      StageTimer tm(c, 0);
+      a.n_tiles = T.T;
+      a.tg = T.tg;
+      a.tm0 = T.tm0;
+      a.tm1 = T.tm1;
+      a.single = T.single;
+      a.members = d_members;
+      a.tile_emit = W.tile_emit;
+      a.fm = &FM;
+      launch_ds<M>(DS_FOLD_MULTI, a);
+    });
+    if (!ok) return fail(OTSDB_E_UNSUPPORTED, "downsampler %d", s0->ds_agg_id);
+    ++c->n_multi_ds;
+    ++c->n_multi_fold;
+    if (T.MG > 0) {
+      StageTimer tm(c, 2);
+      for (int i = 0; i < q.n; ++i) {
+        Work Ws = W;
+        Ws.partial = FM.kind[i] == FM_MIN   ? FM.part_mn
+                     : FM.kind[i] == FM_MAX ? FM.part_mx
+                                            : FM.part_sn;
+        with_monoid(q.aggs[i], [&](auto tag) {
+          launch_combine<decltype(tag)>(c, Ws, NB, T.MG, T.mg, T.mt0, T.mt1,
+                                        out_val[i], out_emit[i], nullptr,
+                                        two_level, 0, c->d_merr + q.e0 + i);
+        });
+      }
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return multi_compact_outputs(c, q, P, G, out_val, out_emit);
+}
+
 otsdb_status run_multi_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
                             const Req& q, const otsdb_batch* b,
-                            std::vector<int64_t>& goff) {
+                            std::vector<int64_t>& goff, bool may_fold = true) {
   c->multi_failed = -1;
+  c->n_multi_fold = 0;
   if (q.n == 1 || !(spec->ds_interval_ms > 0 || spec->run_all) ||
       anchored(spec))
     return multi_sequential(c, spec, q, b, goff);
@@ -2640,6 +2832,8 @@ otsdb_status run_multi_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   if (misaligned(b) || !multi_shares_rows(spec, q, P, b->n_series, goff))
     return multi_sequential(c, spec, q, b, goff);
   const BatchDev B = batch_dev(b);
+  if (may_fold && multi_folds(&s0, q, P))
+    return multi_fold(c, &s0, q, B, b->group_members, goff, P);
   MultiState M;
   rc = multi_build(c, &s0, q, B, b->group_members, goff, P, nullptr, nullptr, M);
   if (rc) return rc;
@@ -2923,7 +3117,10 @@ otsdb_status run_panel_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
     otsdb_query_spec sf = *spec;
     sf.ds_agg_id = f.ds;
     c->result_short = false;
-    O.record(c, f, run_multi_impl(c, &sf, f.req(q, 0), b, goff));
+    // (OTSDB_SPEC_MULTI_FOLD: a panel of one distinct function is the multi
+    // call; several functions keep the row path)
+    O.record(c, f, run_multi_impl(c, &sf, f.req(q, 0), b, goff,
+                                  /*may_fold=*/F.size() == 1));
   }
   return O.publish(c, q.n);
 }
@@ -3196,7 +3393,7 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   otsdb_batch cb;
   rc = cells_columnar(c, cells, b, &cb);
   if (rc) return rc;
-  if (mq) return run_multi_impl(c, spec, *mq, &cb, goff);
+  if (mq) return run_multi_impl(c, spec, *mq, &cb, goff, /*may_fold=*/false);
   return run_device_impl(c, spec, &cb, out, goff);
 }
 
@@ -5136,12 +5333,13 @@ otsdb_status otsdb_prof_read(otsdb_ctx* c, double* ms, int64_t* launches,
 otsdb_status otsdb_ctx_counters(otsdb_ctx* c, int64_t* out, int n) {
   if (!c || (n > 0 && !out)) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
   CtxLock lk(c, /*keep_session=*/true);
-  const int64_t v[12] = {c->n_cells_uniform, c->n_cells_general,
+  const int64_t v[13] = {c->n_cells_uniform, c->n_cells_general,
                          c->n_cells_uni_miss, c->sel.key_reads, c->sel.passes,
                          c->n_multi_ds,       c->n_multi_group, c->n_multi_kt,
                          c->n_multi_tf,       c->sel.sessions,
-                         c->n_panel_passes,   c->n_panel_mats};
-  for (int i = 0; i < n && i < 12; ++i) out[i] = v[i];
+                         c->n_panel_passes,   c->n_panel_mats,
+                         c->n_multi_fold};
+  for (int i = 0; i < n && i < 13; ++i) out[i] = v[i];
   return OTSDB_OK;
 }
 

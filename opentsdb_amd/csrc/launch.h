@@ -1,8 +1,9 @@
 // launch.h — the host-side record through which the engine launches the
 // kernels templated on the DOWNSAMPLING monoid.  Those kernels (k_prep, the
 // ring k_bucketize_k, the rate-fused one, k_bucketize_cells, k_fold_prep and
-// the ordered group fold k_fold x every aggregator) are compiled in one
-// translation unit per downsampling monoid (ds_tu.hip), in parallel.
+// the ordered group fold k_fold x every aggregator, k_fold_multi over the
+// envelope state) are compiled in one translation unit per downsampling
+// monoid (ds_tu.hip), in parallel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -112,7 +113,27 @@ enum DsKernel {
   DS_PREP_FOLD,   // k_prep_fold: k_prep + k_fold_prep in one launch
   DS_CELLS_UNIFORM, // k_cells_uniform: which kept series are uniform
   DS_CELLS_FOLD2U,  // the uniform cells fold (fold_member_cells_u), 2-byte
-  DS_CELLS_FOLD4U   // ... 4-byte qualifiers
+  DS_CELLS_FOLD4U,  // ... 4-byte qualifiers
+  DS_FOLD_MULTI     // k_fold_multi: the fold over the envelope state, one
+                    // pass for every output of a multi-aggregator call
+};
+
+// What a multi-aggregator fold (k_fold_multi, foldmulti.hip) finishes from
+// the envelope state: the kind of each output and where it goes.
+enum : int32_t { FM_SUM = 0, FM_AVG = 1, FM_CNT = 2, FM_MIN = 3, FM_MAX = 4 };
+struct FoldMultiOut {
+  double* val;    // [G * nb]
+  uint8_t* emit;  // [G * nb]
+  int* err;       // this output's device error word
+};
+struct FoldMultiArgs {
+  int32_t n_out;
+  int32_t kind[OTSDB_MULTI_MAX];  // FM_* of output j
+  FoldMultiOut out[OTSDB_MULTI_MAX];
+  // tiles of a group of several: the partials k_combine<M> merges per output,
+  // [n_tiles * nb] each, null when no output needs them — (s, n) for sum /
+  // avg / count (MSum<*>::pack), mn for min, mx for max (MMinMax<*>::pack)
+  Packed *part_sn, *part_mn, *part_mx;
 };
 
 struct DsLaunch {
@@ -140,6 +161,8 @@ struct DsLaunch {
   int agg_id;
   // DS_CELLS_PREP / DS_CELLS_FOLD
   CellsFold cf;
+  // DS_FOLD_MULTI (beside DS_FOLD's tiles, windows and tile_emit)
+  const FoldMultiArgs* fm;
 };
 
 // Debug builds (-DOTSDB_DEBUG_SYNC): every launch reports itself and waits

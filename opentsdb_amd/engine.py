@@ -208,6 +208,12 @@ class Engine:
         return dict(downsample_passes=out[5], group_passes=out[6],
                     key_transposes=out[7], transform_passes=out[8])
 
+    def multi_fold_counters(self):
+        """Of the last multi-aggregator call (otsdb_ctx_counters [12]):
+        multi-aggregator folds launched — 1 when the call asked for the fold
+        (fold=True) and was eligible, else 0."""
+        return dict(fold_launches=int(self._counters(13)[12]))
+
     def panel_counters(self):
         """Of the last panel call (otsdb_ctx_counters [10..11]): passes over
         the point stream (one for all envelope functions that share a pass,
@@ -269,11 +275,16 @@ class Engine:
             C.byref(batch.as_abi()), C.byref(sz)))
         return sz
 
-    def run_multi(self, spec, aggs, batch, interps=None):
+    def run_multi(self, spec, aggs, batch, interps=None, fold=False):
         """Several cross-series aggregators over one downsample pass of the
         same query (host arrays): `spec` with its aggregator replaced by each
         of `aggs` in turn.  Returns one list of DataPoints (one per group)
-        per aggregator, each what run() gives for that aggregator."""
+        per aggregator, each what run() gives for that aggregator.
+        fold: ask for the multi-aggregator fold (abi.SPEC_MULTI_FOLD on a
+        copy of the spec): sum / avg / count / min / max sets of one
+        interpolation take one ordered fold and no row matrix; a request that
+        is not eligible runs as without it."""
+        spec = _fold_spec(spec, fold)
         n, ids, it = multi_args(aggs, interps)
         sz = self.plan_multi(spec, ids, batch, it)
         rs, points = _host_results(n, batch.n_groups,
@@ -439,11 +450,22 @@ def run_device(engine, spec, dbatch, dresult, stream=None):
         None if stream is None else C.c_void_p(stream)))
 
 
+def _fold_spec(spec, fold):
+    """spec, or a copy with abi.SPEC_MULTI_FOLD set (the caller's spec is
+    never written)."""
+    if not fold:
+        return spec
+    s = type(spec).from_buffer_copy(spec)
+    s.flags |= abi.SPEC_MULTI_FOLD
+    return s
+
+
 def run_multi_device(engine, spec, aggs, dbatch, dresults, stream=None,
-                     interps=None):
+                     interps=None, fold=False):
     """Device-resident multi-aggregator call: dresults[i] (a DeviceResult)
     takes what run_device gives for aggs[i]; the point stream is downsampled
-    once for all of them."""
+    once for all of them.  fold: as Engine.run_multi's."""
+    spec = _fold_spec(spec, fold)
     n, ids, it = multi_args(aggs, interps)
     rs = _result_array(dresults, n, "aggregators")
     b = _abi_cached(dbatch, _BATCH_TENSORS, dbatch.as_abi,
