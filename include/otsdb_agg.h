@@ -121,6 +121,7 @@ typedef enum {
 /* ------------------------------------------------------------------------ */
 #define OTSDB_SPEC_EXACT_ORDER 1
 #define OTSDB_SPEC_MULTI_FOLD 2 /* otsdb_agg_run_multi*: see there */
+#define OTSDB_SPEC_CELLS_MULTI_FOLD 4 /* otsdb_agg_run_cells_multi_device */
 typedef struct {
   /* AggregationIterator window, ms, inclusive on both ends
    * (SpanGroup ctor normalises the scan bounds to ms, SpanGroup.java:267-270;
@@ -316,7 +317,8 @@ otsdb_status otsdb_agg_run_device(otsdb_ctx* ctx, const otsdb_query_spec* spec,
  * within 1e-12 of it otherwise (sum / avg downsampling on wider grids: the
  * fold's windows differ).  Every other request ignores the
  * flag and runs exactly as without it ([12] = 0); the cells and partials
- * entries never read it.
+ * entries never read it (the cells entry has a bit of its own,
+ * OTSDB_SPEC_CELLS_MULTI_FOLD).
  * plan_multi: max_out_points bounds EACH output, workspace_bytes the call.  */
 #define OTSDB_MULTI_MAX 32
 otsdb_status otsdb_agg_plan_multi(otsdb_ctx* ctx, const otsdb_query_spec* spec,
@@ -631,7 +633,20 @@ otsdb_status otsdb_agg_run_cells_device(otsdb_ctx* ctx,
                                         otsdb_result* out, void* hip_stream);
 /* Several aggregators over one decode + downsample of the columns
  * (otsdb_agg_run_multi_device's contract; the routing between the fused
- * decode and the columnar buffer is otsdb_agg_run_cells_device's).          */
+ * decode and the columnar buffer is otsdb_agg_run_cells_device's).
+ * spec->flags & OTSDB_SPEC_CELLS_MULTI_FOLD (opt-in, read by this entry and
+ * by otsdb_agg_run_cells_panel_device for a request of one distinct
+ * downsampling function, by no other): a request OTSDB_SPEC_MULTI_FOLD would
+ * fold from columns — envelope aggregators of one interpolation class on a
+ * downsampled, non-rate query — over a narrow (fixed-interval) grid takes ONE
+ * cells fold over the {sum, count, min, max} state: the columns are decoded
+ * once, no row matrix, no transform, no group pass (otsdb_ctx_counters
+ * [5..8] = 1, 0, 0, 0; [12] = the folds launched: 1, or 2 when the uniform
+ * kernel missed and the general one ran again).  Output i is what
+ * otsdb_agg_run_cells_device gives for aggregator i: bit for bit for an
+ * order-free downsampling function and on grids of up to 128 buckets, within
+ * 1e-12 otherwise.  Columns the cells fold does not take are decoded and run
+ * as without the flag; every other request ignores it ([12] = 0).          */
 otsdb_status otsdb_agg_run_cells_multi_device(otsdb_ctx* ctx,
                                               const otsdb_query_spec* spec,
                                               int32_t n_out,
@@ -769,7 +784,9 @@ otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
  * otsdb_agg_run_panel* call: out[10] passes over the point stream, out[11]
  * row matrices built (the multi calls inside it still maintain [5..8]).
  * out[12]: multi-aggregator folds launched by the last otsdb_agg_*_multi*
- * call (OTSDB_SPEC_MULTI_FOLD on an eligible request: 1, else 0).            */
+ * call (OTSDB_SPEC_MULTI_FOLD on an eligible request: 1, else 0;
+ * OTSDB_SPEC_CELLS_MULTI_FOLD: one per cells fold launched, 2 after a uniform
+ * miss).                                                                    */
 otsdb_status otsdb_ctx_counters(otsdb_ctx* ctx, int64_t* out, int n);
 /* Test hook: the one-pass compaction's epoch (1 .. 2^24 - 1, forward only)
  * the context's next call increments, so tests can drive it to its wrap.  */

@@ -134,6 +134,7 @@ class GenSpec(C.Structure):
 
 SPEC_EXACT_ORDER = 1  # otsdb_query_spec.flags
 SPEC_MULTI_FOLD = 2   # ... a multi call may take the multi-aggregator fold
+SPEC_CELLS_MULTI_FOLD = 4  # ... a cells multi call may take the cells fold
 
 
 EXPORTS = [

@@ -50,9 +50,8 @@
 #include "fold.hip"
 #if OTSDB_DS_PART == 1
 #include "cellfold.hip"
-#else
-#include "foldmulti.hip"
 #endif
+#include "foldmulti.hip"
 
 namespace otsdb {
 
@@ -63,11 +62,34 @@ inline unsigned ds_blocks(int64_t n, int per) {
 }  // namespace
 
 #if OTSDB_DS_PART == 1
-// the cells fold: prep + k_fold<M, A, 8, 1> x every aggregator
+// the cells fold: prep + k_fold<M, A, 8, 1> x every aggregator, and
+// k_fold_multi's cells variants over the envelope state
+template <class M, int CELLS>
+void launch_cells_multi(const DsLaunch& a, const char* what) {
+  hipLaunchKernelGGL((k_fold_multi<M, 8, CELLS>),
+                     dim3((unsigned)(a.n_tiles * a.NW)), dim3(FOLD_THREADS),
+                     (unsigned)fold_lds_bytes<MEnv>(a.P), a.st, a.P, a.B, a.SM,
+                     a.n_tiles, a.tg, a.tm0, a.tm1, a.single, a.members, a.wc,
+                     a.NW, a.tile_emit, a.err, *a.fm, a.cf);
+  OTSDB_DBG(a.st, what);
+}
+
 template <class M>
 bool launch_cells(DsKernel k, const DsLaunch& a) {
   const int64_t S = a.B.S;
   switch (k) {
+    case DS_CELLS_MULTI2:
+      launch_cells_multi<M, 2>(a, "k_fold_multi<cells, qw 2>");
+      return true;
+    case DS_CELLS_MULTI4:
+      launch_cells_multi<M, 4>(a, "k_fold_multi<cells, qw 4>");
+      return true;
+    case DS_CELLS_MULTI2U:
+      launch_cells_multi<M, 10>(a, "k_fold_multi<cells, qw 2, uniform>");
+      return true;
+    case DS_CELLS_MULTI4U:
+      launch_cells_multi<M, 12>(a, "k_fold_multi<cells, qw 4, uniform>");
+      return true;
     case DS_CELLS_PREP:
       if (S > 0)
         hipLaunchKernelGGL(k_cells_prep<M>, dim3(ds_blocks(S, OTSDB_PREP_TPB)),
@@ -223,7 +245,7 @@ bool launch_ds(DsKernel k, const DsLaunch& a) {
                          dim3((unsigned)(a.n_tiles * a.NW)), dim3(FOLD_THREADS),
                          (unsigned)lds, a.st, P, a.B, a.SM, a.n_tiles, a.tg,
                          a.tm0, a.tm1, a.single, a.members, a.wc, a.NW,
-                         a.tile_emit, a.err, *a.fm);
+                         a.tile_emit, a.err, *a.fm, a.cf);
       OTSDB_DBG(a.st, "k_fold_multi");
       return true;
     }

@@ -2648,9 +2648,11 @@ int fold_multi_kind(int agg) {
 // fold instead: the caller asked for it, the single queries would fold
 // (fold_path), every aggregator is a component of the envelope state and all
 // outputs contribute through one interpolation class (the fold bakes it into
-// the contributions as it pushes them).
-bool multi_folds(const otsdb_query_spec* s0, const Req& q, const Params& P) {
-  if (!(s0->flags & OTSDB_SPEC_MULTI_FOLD) || q.n < 2) return false;
+// the contributions as it pushes them).  bit: the flag that asks — the
+// columnar entries' or the cells entry's (OTSDB_SPEC_CELLS_MULTI_FOLD).
+bool multi_folds(const otsdb_query_spec* s0, const Req& q, const Params& P,
+                 int bit = OTSDB_SPEC_MULTI_FOLD) {
+  if (!(s0->flags & bit) || q.n < 2) return false;
   for (int i = 0; i < q.n; ++i) {
     const otsdb_query_spec si = req_spec(s0, q, i);
     if (fold_multi_kind(si.agg_id) < 0 || !fold_path(&si, P, 0)) return false;
@@ -2666,16 +2668,35 @@ bool multi_folds(const otsdb_query_spec* s0, const Req& q, const Params& P) {
 // kernels — then k_combine<M> per output over the tiles of larger groups and
 // the compaction of every output.  No row matrix, no transform, no group
 // pass.
-otsdb_status multi_fold(otsdb_ctx* c, const otsdb_query_spec* s0,
-                        const Req& q, const BatchDev& B,
-                        const int64_t* d_members, std::vector<int64_t>& goff,
-                        const Params& P0) {
+// cells / series_row (as run_pipeline's): the members are streamed from
+// compacted columns — k_cells_prep, k_cells_uniform and k_cells_fold_prep in
+// the prep kernels' place, the cursors sized for THIS state's windows, and
+// k_fold_multi's cells variant chosen from the widths / uniform words as the
+// single cells fold chooses k_fold's.  The pass ends with the launches (the
+// cells attempt loop reads the error word before anything is compacted);
+// multi_fold_finish compacts the outputs.
+struct MultiFoldRun {
+  Params P;
+  int64_t G;
+  double* out_val[OTSDB_MULTI_MAX];
+  uint8_t* out_emit[OTSDB_MULTI_MAX];
+};
+
+otsdb_status multi_fold_pass(otsdb_ctx* c, const otsdb_query_spec* s0,
+                             const Req& q, const BatchDev& B,
+                             const int64_t* d_members,
+                             std::vector<int64_t>& goff, const Params& P0,
+                             const CellsDev* cells, const int64_t* series_row,
+                             MultiFoldRun& X) {
   hipStream_t st = c->stream;
   otsdb_status rc = multi_buffers(c);
   if (rc) return rc;
-  Params P = P0;
+  Params& P = X.P;
+  P = P0;
+  double** const out_val = X.out_val;
+  uint8_t** const out_emit = X.out_emit;
   const int64_t S = B.S, NB = P.nb;
-  const int64_t G = (int64_t)goff.size() - 1;
+  const int64_t G = X.G = (int64_t)goff.size() - 1;
   int cls[OTSDB_MULTI_MAX], ci[OTSDB_MULTI_MAX];
   multi_classes(q, P, cls, ci);
   P.interp = ci[0];
@@ -2724,8 +2745,12 @@ otsdb_status multi_fold(otsdb_ctx* c, const otsdb_query_spec* s0,
   const bool two_level = two_level_combine(T.max_chunks, T.MG, NB);
   Work W;
   WinCtx* wc = nullptr;
-  double* out_val[OTSDB_MULTI_MAX];
-  uint8_t* out_emit[OTSDB_MULTI_MAX];
+  CellsFold CF{};
+  if (cells) {
+    CF.C = *cells;
+    CF.series_row = series_row;
+    CF.wide = c->d_err + 1;
+  }
   auto carve = [&](char* base) {
     Carve cv{base};
     carve_series(cv, W, S);
@@ -2739,6 +2764,18 @@ otsdb_status multi_fold(otsdb_ctx* c, const otsdb_query_spec* s0,
       out_emit[i] = cv.take<uint8_t>((size_t)G * NB);
     }
     if (NW > 1) wc = cv.take<WinCtx>((size_t)S * (NW - 1));
+    if (cells) {  // (NW: this state's windows, not the single query's)
+      CF.rlo = cv.take<int64_t>(S);
+      CF.vlo = cv.take<int64_t>(S);
+      CF.qw = cv.take<uint8_t>(S);
+      CF.vl0 = cv.take<uint8_t>(S);
+      CF.uf = cv.take<uint8_t>(S);
+      if (NW > 1) {
+        CF.wrlo = cv.take<int64_t>((size_t)S * (NW - 1));
+        CF.wvlo = cv.take<int64_t>((size_t)S * (NW - 1));
+        CF.wvl0 = cv.take<uint8_t>((size_t)S * (NW - 1));
+      }
+    }
     if (two_level) carve_combine(cv, W, T.MG, NB);
     return cv.off + 256;
   };
@@ -2761,7 +2798,12 @@ otsdb_status multi_fold(otsdb_ctx* c, const otsdb_query_spec* s0,
       HIP_TRY(hipMemsetAsync(out_emit[i], 0, (size_t)G * NB, st));
   for (int i = 0; i < q.n; ++i)
     FM.out[i] = FoldMultiOut{out_val[i], out_emit[i], c->d_merr + q.e0 + i};
-  multi_counters(c, 0, 0);
+  {
+    // (the cells attempts of one call add their fold launches up)
+    const int64_t folds = cells ? c->n_multi_fold : 0;
+    multi_counters(c, 0, 0);
+    c->n_multi_fold = folds;
+  }
   // (multi_shares_rows: series, members and buckets exist, so every dense
   // output below is written by the fold or by k_combine)
   if (S > 0 && NB > 0 && T.T > 0) {
@@ -2773,7 +2815,12 @@ otsdb_status multi_fold(otsdb_ctx* c, const otsdb_query_spec* s0,
         a.wc = wc;
         a.NW = NW;
         a.WB = WB;
-        if (NW > 1 && S * (NW - 1) <= prep_fold_max()) {
+        if (cells) {
+          a.cf = CF;
+          launch_cells<M>(DS_CELLS_PREP, a);
+          if (!c->cells_no_uni) launch_cells<M>(DS_CELLS_UNIFORM, a);
+          if (NW > 1) launch_cells<M>(DS_CELLS_FOLD_PREP, a);
+        } else if (NW > 1 && S * (NW - 1) <= prep_fold_max()) {
           launch_ds<M>(DS_PREP_FOLD, a);
         } else {
           launch_ds<M>(DS_PREP, a);
@@ -2789,11 +2836,40 @@ otsdb_status multi_fold(otsdb_ctx* c, const otsdb_query_spec* s0,
       a.members = d_members;
       a.tile_emit = W.tile_emit;
       a.fm = &FM;
-      launch_ds<M>(DS_FOLD_MULTI, a);
+      if (!cells) {
+        launch_ds<M>(DS_FOLD_MULTI, a);
+        ++c->n_multi_fold;
+        return;
+      }
+      // the kernel with the qualifier width fixed, uniform or general: the
+      // single cells fold's choice (run_pipeline) from k_cells_prep's widths
+      // (bits 0 / 1: 4- / 2-byte series kept; both: ERR_CELLS_GENERIC, the
+      // attempt loop rewrites the columns) and k_cells_uniform's bit 2
+      int widths = 3;
+      bool uniform = false;
+      if (hipMemcpyAsync(&c->h_small[2], c->d_err, 2 * sizeof(int),
+                         hipMemcpyDeviceToHost, st) == hipSuccess &&
+          hipStreamSynchronize(st) == hipSuccess) {
+        widths = (int)((c->h_small[2] >> 32) & 3);
+        uniform = !c->cells_no_uni && !((c->h_small[2] >> 32) & 4);
+      }
+      if (widths == 3) {
+        const int e = (int)(c->h_small[2] & 0xFFFFFFFF) | ERR_CELLS_GENERIC;
+        c->h_small[3] = e;
+        hipMemcpyAsync(c->d_err, &c->h_small[3], sizeof(int),
+                       hipMemcpyHostToDevice, st);
+      } else if (uniform) {
+        launch_cells<M>(widths == 1 ? DS_CELLS_MULTI4U : DS_CELLS_MULTI2U, a);
+        ++c->n_cells_uniform;
+        ++c->n_multi_fold;
+      } else {
+        launch_cells<M>(widths == 1 ? DS_CELLS_MULTI4 : DS_CELLS_MULTI2, a);
+        ++c->n_cells_general;
+        ++c->n_multi_fold;
+      }
     });
     if (!ok) return fail(OTSDB_E_UNSUPPORTED, "downsampler %d", s0->ds_agg_id);
     ++c->n_multi_ds;
-    ++c->n_multi_fold;
     if (T.MG > 0) {
       StageTimer tm(c, 2);
       for (int i = 0; i < q.n; ++i) {
@@ -2810,7 +2886,22 @@ otsdb_status multi_fold(otsdb_ctx* c, const otsdb_query_spec* s0,
     }
   }
   HIP_TRY(hipGetLastError());
-  return multi_compact_outputs(c, q, P, G, out_val, out_emit);
+  return OTSDB_OK;
+}
+
+otsdb_status multi_fold_finish(otsdb_ctx* c, const Req& q,
+                               const MultiFoldRun& X) {
+  return multi_compact_outputs(c, q, X.P, X.G, X.out_val, X.out_emit);
+}
+
+otsdb_status multi_fold(otsdb_ctx* c, const otsdb_query_spec* s0,
+                        const Req& q, const BatchDev& B,
+                        const int64_t* d_members, std::vector<int64_t>& goff,
+                        const Params& P0) {
+  MultiFoldRun X;
+  const otsdb_status rc = multi_fold_pass(c, s0, q, B, d_members, goff, P0,
+                                          nullptr, nullptr, X);
+  return rc ? rc : multi_fold_finish(c, q, X);
 }
 
 otsdb_status run_multi_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
@@ -3340,8 +3431,10 @@ otsdb_status cells_attempts(otsdb_ctx* c, const otsdb_cells* cells, int64_t S,
 // the query and the columns allow it, else decode -> columnar -> pipeline.
 // mq: several aggregators (otsdb_agg_run_cells_multi_device; `spec` carries
 // output 0's, `out` is unused): the same routing, with the shared-rows
-// pipeline in place of run_pipeline where the outputs can share them, and
-// run_multi_impl over the decoded columns otherwise.
+// pipeline in place of run_pipeline where the outputs can share them (with
+// OTSDB_SPEC_CELLS_MULTI_FOLD on an eligible request: the cells fold over
+// the envelope state in its place, multi_fold_pass), and run_multi_impl over
+// the decoded columns otherwise (never folded).
 otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
                             const otsdb_cells* cells, const otsdb_batch* b,
                             otsdb_result* out, std::vector<int64_t>& goff,
@@ -3363,10 +3456,20 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
     const BatchDev B{S, nullptr, nullptr, nullptr, nullptr, nullptr};
     Work W;
     MultiState MS;
+    MultiFoldRun MF;
     CellsEnd end;
+    // OTSDB_SPEC_CELLS_MULTI_FOLD: the cells fold over the envelope state in
+    // the row pass's place (narrow grids, as the single cells fold; calendar
+    // grids from cells keep the rows)
+    const bool mfold = mq && !c->verbatim && P.narrow &&
+                       multi_folds(spec, *mq, P, OTSDB_SPEC_CELLS_MULTI_FOLD);
+    if (mq) c->n_multi_fold = 0;
     rc = cells_attempts(
         c, cells, S, P, &end,
         [&](const CellsDev& CQ, const int64_t* series_row) {
+          if (mfold)
+            return multi_fold_pass(c, spec, *mq, B, b->group_members, goff, P,
+                                   &CQ, series_row, MF);
           if (mq) {  // (every attempt its own work set)
             MS = MultiState();
             return multi_build(c, spec, *mq, B, b->group_members, goff, P, &CQ,
@@ -3377,6 +3480,7 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
                               nullptr, nullptr, &CQ, series_row);
         },
         [&]() {
+          if (mfold) return multi_fold_finish(c, *mq, MF);
           if (mq) return multi_aggregate(c, MS);
           const int64_t G = (int64_t)goff.size() - 1;
           const otsdb_status rf =
@@ -3517,6 +3621,9 @@ otsdb_status run_cells_panel_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   auto run_func = [&](PanelFunc& f) {
     otsdb_query_spec sf = *spec;
     sf.ds_agg_id = f.ds;
+    // (OTSDB_SPEC_CELLS_MULTI_FOLD: only a panel of one distinct function is
+    // the cells multi call and inherits the bit)
+    if (F.size() != 1) sf.flags &= ~OTSDB_SPEC_CELLS_MULTI_FOLD;
     c->result_short = false;
     O.record(c, f, run_cells_req(c, &sf, f.req(q, 0), cells, b, goff));
   };

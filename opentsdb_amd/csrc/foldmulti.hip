@@ -13,7 +13,13 @@
 // Only the finalisation differs from k_fold: a whole-group tile writes every
 // output (Infinity into the error word of the output that holds it), a tile
 // of a larger group leaves the per-monoid partials k_combine<M> merges.
-// (Included by ds_tu.hip part 0 after fold.hip.)
+// CELLS != 0 (otsdb_agg_run_cells_multi_device with
+// OTSDB_SPEC_CELLS_MULTI_FOLD): the members are streamed from compacted
+// columns — k_fold's CELLS variants (the CellsMember slot per wave, the
+// ERR_CELLS_GENERIC early-out, fold_member_cells / fold_member_cells_u of
+// cellfold.hip, the cells fold's launch bound) over the same state.
+// (Included by both parts of ds_tu.hip: the columnar kernel is launched from
+// part 0, the cells ones from part 1.)
 #pragma once
 #include "fold.hip"
 #include "menv.h"
@@ -32,15 +38,20 @@ DEV double fold_multi_finish(const MEnv& m, int32_t kind) {
   }
 }
 
-template <class M, int K = 8>
-__global__ __launch_bounds__(FOLD_THREADS, OTSDB_FOLD_WAVES) void k_fold_multi(
+#ifndef OTSDB_CELLS_MULTI_FOLD_WAVES  // (tuning builds: another bound)
+#define OTSDB_CELLS_MULTI_FOLD_WAVES OTSDB_CELLS_FOLD_WAVES
+#endif
+
+template <class M, int K = 8, int CELLS = 0>
+__global__ __launch_bounds__(FOLD_THREADS, CELLS ? OTSDB_CELLS_MULTI_FOLD_WAVES
+                                        : OTSDB_FOLD_WAVES) void k_fold_multi(
     Params P, BatchDev B, SeriesMeta SM, int64_t n_tiles,
     const int64_t* __restrict__ tile_g, const int64_t* __restrict__ tile_m0,
     const int64_t* __restrict__ tile_m1,
     const uint8_t* __restrict__ tile_single,
     const int64_t* __restrict__ members, const WinCtx* __restrict__ wc,
     int64_t NW, uint8_t* __restrict__ tile_emit, int* err_word,
-    FoldMultiArgs FM) {
+    FoldMultiArgs FM, CellsFold CF) {
   using A = MEnv;
   // the window's envelope states and emit flags (fold_lds_bytes<MEnv>: 1,024
   // buckets at most, 33,792 B)
@@ -52,6 +63,7 @@ __global__ __launch_bounds__(FOLD_THREADS, OTSDB_FOLD_WAVES) void k_fold_multi(
   __shared__ int s_next;
   __shared__ FoldKernel kc;
   __shared__ FoldMember mc[FOLD_WG];
+  __shared__ CellsMember cm[CELLS ? FOLD_WG : 1];
   const int tid = threadIdx.x, lane = LANE, w = tid >> 6;
   const int64_t nb = P.nb;
   int32_t W0, W1;
@@ -77,7 +89,11 @@ __global__ __launch_bounds__(FOLD_THREADS, OTSDB_FOLD_WAVES) void k_fold_multi(
       kc.out_val = nullptr;
       kc.out_emit = nullptr;
       kc.fin = tile_single[t];
-      s_next = 0;
+      // a cells fold whose prep already sent the batch to the generic path
+      // (as k_fold: the engine rewrites the columns and runs again)
+      s_next = (CELLS && (__hip_atomic_load(err_word, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT) &
+                          ERR_CELLS_GENERIC)) ? -1 : 0;
     }
   }
   const int nw = W1 - W0;
@@ -88,6 +104,7 @@ __global__ __launch_bounds__(FOLD_THREADS, OTSDB_FOLD_WAVES) void k_fold_multi(
   for (int j = tid; j < 256; j += FOLD_THREADS) prog[j] = 0;
   for (int i = lane; i < FOLD_WIN; i += 64) ring[w][i] = absent_value();
   __syncthreads();
+  if (CELLS && s_next < 0) return;  // (block-uniform)
   int dbg_n = 0;
   FoldSink<A> F{st, emit, ring[w], prog, err_word, 0, 0, W0, W1, W0, -1, 0, 0.0};
   // a member's window context (k_prep / k_fold_prep's results for series s)
@@ -130,7 +147,7 @@ __global__ __launch_bounds__(FOLD_THREADS, OTSDB_FOLD_WAVES) void k_fold_multi(
   // every member context loaded at once when the host sized the dynamic LDS
   // for them (P.fold_ctx > 0: windows short of full width)
   const int64_t n_mem = kc.m1 - kc.m0;
-  const bool ctx_on = P.fold_ctx > 0 && n_mem <= P.fold_ctx;
+  const bool ctx_on = !CELLS && P.fold_ctx > 0 && n_mem <= P.fold_ctx;
   FoldMember* ctx = reinterpret_cast<FoldMember*>(fold_dyn + fold_lds_bytes<A>(P));
   if (ctx_on) {
     for (int64_t j = tid; j < n_mem; j += FOLD_THREADS) ctx[j] = member_ctx(kc.members[kc.m0 + j]);
@@ -146,8 +163,38 @@ __global__ __launch_bounds__(FOLD_THREADS, OTSDB_FOLD_WAVES) void k_fold_multi(
     F.mi = i;
     F.eff = 0;
     // the member's window context, lane 0 -> LDS (preloaded: a copy)
-    if (lane == 0) mc[w] = ctx_on ? ctx[i] : member_ctx(kc.members[m0 + i]);
-    fold_member<M, A, K>(P, B, F, &mc[w]);
+    if (lane == 0) {
+      const int64_t s = ctx_on ? 0 : kc.members[m0 + i];
+      mc[w] = ctx_on ? ctx[i] : member_ctx(s);
+      if (CELLS) {  // the stream's cursor at the window's first point
+        const int64_t nbd = kc.nbd, win = kc.win;
+        CellsMember c;
+        c.qb = CF.C.qual_off[CF.series_row[s]];
+        c.vb0 = CF.C.val_off[CF.series_row[s]];
+        c.r1 = CF.series_row[s + 1];
+        if (win > 0) {
+          const int64_t o = s * nbd + win - 1;
+          c.rlo = CF.wrlo[o];
+          c.vcur = CF.wvlo[o];
+          c.vl0 = CF.wvl0[o];
+        } else {
+          c.rlo = CF.rlo[s];
+          c.vcur = CF.vlo[s];
+          c.vl0 = CF.vl0[s];
+        }
+        c.qw = CF.qw[s];
+        c.uf = CF.uf ? CF.uf[s] : 0xFF;
+        c.qend = CF.C.qual_off[CF.C.R];
+        c.vend = CF.C.val_off[CF.C.R];
+        cm[CELLS ? w : 0] = c;
+      }
+    }
+    if constexpr (CELLS >= 8)  // every kept series uniform (k_cells_uniform)
+      fold_member_cells_u<M, A, K, CELLS - 8>(P, CF.C, F, &mc[w], &cm[w]);
+    else if constexpr (CELLS != 0)
+      fold_member_cells<M, A, K, CELLS>(P, CF.C, F, &mc[w], &cm[w]);
+    else
+      fold_member<M, A, K>(P, B, F, &mc[w]);
     fold_publish(F, kProgDone);
   }
   __syncthreads();

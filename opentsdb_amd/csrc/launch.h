@@ -114,8 +114,12 @@ enum DsKernel {
   DS_CELLS_UNIFORM, // k_cells_uniform: which kept series are uniform
   DS_CELLS_FOLD2U,  // the uniform cells fold (fold_member_cells_u), 2-byte
   DS_CELLS_FOLD4U,  // ... 4-byte qualifiers
-  DS_FOLD_MULTI     // k_fold_multi: the fold over the envelope state, one
+  DS_FOLD_MULTI,    // k_fold_multi: the fold over the envelope state, one
                     // pass for every output of a multi-aggregator call
+  DS_CELLS_MULTI2,  // k_fold_multi from compacted columns (launch_cells):
+  DS_CELLS_MULTI4,  // the general member walker, 2- / 4-byte qualifiers
+  DS_CELLS_MULTI2U, // ... the uniform one (fold_member_cells_u)
+  DS_CELLS_MULTI4U
 };
 
 // What a multi-aggregator fold (k_fold_multi, foldmulti.hip) finishes from
@@ -161,7 +165,8 @@ struct DsLaunch {
   int agg_id;
   // DS_CELLS_PREP / DS_CELLS_FOLD
   CellsFold cf;
-  // DS_FOLD_MULTI (beside DS_FOLD's tiles, windows and tile_emit)
+  // DS_FOLD_MULTI / DS_CELLS_MULTI* (beside DS_FOLD's tiles, windows and
+  // tile_emit; the cells ones with cf)
   const FoldMultiArgs* fm;
 };
 

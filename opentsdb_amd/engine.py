@@ -450,13 +450,14 @@ def run_device(engine, spec, dbatch, dresult, stream=None):
         None if stream is None else C.c_void_p(stream)))
 
 
-def _fold_spec(spec, fold):
+def _fold_spec(spec, fold, bit=None):
     """spec, or a copy with abi.SPEC_MULTI_FOLD set (the caller's spec is
-    never written)."""
+    never written).  bit: another flag bit in its place
+    (abi.SPEC_CELLS_MULTI_FOLD for the cells entry)."""
     if not fold:
         return spec
     s = type(spec).from_buffer_copy(spec)
-    s.flags |= abi.SPEC_MULTI_FOLD
+    s.flags |= abi.SPEC_MULTI_FOLD if bit is None else bit
     return s
 
 

@@ -272,11 +272,17 @@ def run_cells_device(engine, spec, cells, db_groups, result):
 
 
 def run_cells_multi_device(engine, spec, aggs, cells, db_groups, results,
-                           interps=None):
+                           interps=None, fold=False):
     """otsdb_agg_run_cells_multi_device: several aggregators over one decode
-    + downsample of the compacted columns; results[i] takes aggs[i]'s."""
+    + downsample of the compacted columns; results[i] takes aggs[i]'s.
+    fold: ask for the multi-aggregator cells fold
+    (abi.SPEC_CELLS_MULTI_FOLD on a copy of the spec): an eligible request —
+    sum / zimsum / pfsum / avg / count / min / mimmin / max / mimmax outputs
+    of one interpolation class over a narrow grid — is decoded and folded
+    once, with no row matrix; any other runs as without it."""
     import ctypes as C
-    from .engine import _result_array, multi_args
+    from .engine import _fold_spec, _result_array, multi_args
+    spec = _fold_spec(spec, fold, abi.SPEC_CELLS_MULTI_FOLD)
     n, ids, it = multi_args(aggs, interps)
     rs = _result_array(results, n, "aggregators", cached=False)
     b = _cells_batch(cells, db_groups)
