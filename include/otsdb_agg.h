@@ -50,9 +50,12 @@ typedef enum {
   OTSDB_E_ILLEGAL_ARGUMENT = 3,
   /* NoSuchElementException: unknown aggregator (Aggregators.java:222-228). */
   OTSDB_E_NO_SUCH_ELEMENT = 4,
-  /* Valid in the reference but not implemented by this engine (calendar
-   * downsampling, rollups, histograms, scalar fill): the Java side keeps its
-   * own iterators for such queries.                                         */
+  /* Valid in the reference but not implemented by this engine (histograms,
+   * scalar fill, rollup avg downsampled with another function, rollup
+   * queries without a downsampler or over per-series calendar anchors): the
+   * Java side keeps its own iterators for such queries.  Also what the
+   * reference itself refuses with UnsupportedOperationException (a rollup
+   * table's dev).                                                           */
   OTSDB_E_UNSUPPORTED = 5,
   /* HIP runtime failure / out of device memory.                            */
   OTSDB_E_DEVICE = 6,
@@ -285,6 +288,49 @@ otsdb_status otsdb_agg_run(otsdb_ctx* ctx, const otsdb_query_spec* spec,
 otsdb_status otsdb_agg_run_device(otsdb_ctx* ctx, const otsdb_query_spec* spec,
                                   const otsdb_batch* batch, otsdb_result* out,
                                   void* hip_stream);
+
+/* ---- rollup queries ------------------------------------------------------ */
+/* The single query over the points of a ROLLUP table (pre-aggregated cells):
+ * the reference hands Downsampler / FillingDownsampler a RollupQuery and
+ * computes two downsampling functions differently (Downsampler.java:162-228,
+ * FillingDownsampler.java:196-252).  With R = rollup_agg_id
+ * (RollupQuery.getRollupAgg()) and F = spec->ds_agg_id, a bucket's value over
+ * its points in time order is
+ *   R = avg, F = avg             sum of the values / sum of value_count (a
+ *                                Java long: it wraps); NaN is NOT skipped; a
+ *                                total count of 0 gives a present 0.0
+ *   R not avg / dev, F = count   the sum of the values (they are counts),
+ *                                NaN not skipped
+ *   R not avg / dev, other F     F as in otsdb_agg_run: the result is that
+ *                                call's, value_count is ignored
+ *   R = dev                      OTSDB_E_UNSUPPORTED (the reference throws)
+ *   R = avg, F not avg           OTSDB_E_UNSUPPORTED (not built; TsdbQuery
+ *                                always makes R = F, TsdbQuery.java:1746-1748)
+ * Output points are doubles; bucket timestamps, seek, "all", the filling
+ * grid, rate, interpolation, every aggregator and the compaction are the
+ * single query's over these bucket values.
+ * value_count[i] is point i's valueCount() (RollupSeq.java:659-679) — the
+ * (sum, count) pairs RollupSeq's iterator yields after its sync(): pairing
+ * sum and count cells stays with the caller.  Required when R = avg (NULL:
+ * OTSDB_E_ILLEGAL_ARGUMENT; 16-byte aligned like ts_ms / val on the device
+ * entry), otherwise ignored and may be NULL.
+ * A spec without a downsampler (ds_interval_ms == 0 and no run_all) or with
+ * per-series calendar anchors (n_cal_anchors > 0): OTSDB_E_UNSUPPORTED; an
+ * unknown rollup_agg_id: OTSDB_E_NO_SUCH_ELEMENT.  otsdb_agg_plan's n_buckets
+ * and max_out_points hold for these calls unchanged.                        */
+otsdb_status otsdb_agg_run_rollup_device(otsdb_ctx* ctx,
+                                         const otsdb_query_spec* spec,
+                                         const otsdb_batch* batch,
+                                         int32_t rollup_agg_id,
+                                         const int64_t* value_count,
+                                         otsdb_result* out, void* hip_stream);
+/* Host pointers throughout (value_count too); otsdb_agg_run's
+ * OTSDB_E_CAPACITY contract holds.                                          */
+otsdb_status otsdb_agg_run_rollup(otsdb_ctx* ctx, const otsdb_query_spec* spec,
+                                  const otsdb_batch* batch,
+                                  int32_t rollup_agg_id,
+                                  const int64_t* value_count,
+                                  otsdb_result* out);
 
 /* ---- several aggregators over one downsample pass ----------------------- */
 /* The sub-queries of one panel that differ only in the cross-series

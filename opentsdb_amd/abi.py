@@ -158,6 +158,7 @@ EXPORTS = [
     "otsdb_sel_retarget",
     "otsdb_agg_plan_panel", "otsdb_agg_run_panel_device",
     "otsdb_agg_run_panel", "otsdb_agg_run_cells_panel_device",
+    "otsdb_agg_run_rollup_device", "otsdb_agg_run_rollup",
 ]
 
 MULTI_MAX = 32  # OTSDB_MULTI_MAX
@@ -289,6 +290,14 @@ def load(path=None):
         lib.otsdb_agg_run_cells_panel_device.argtypes = [vp, PS, i32, vp, vp,
                                                          vp, PC, PB, PR, vp]
         lib.otsdb_agg_run_cells_panel_device.restype = C.c_int
+    # rollup queries: (ctx, spec, batch, rollup_agg_id, value_count[N],
+    # result [, stream])
+    if hasattr(lib, "otsdb_agg_run_rollup"):
+        lib.otsdb_agg_run_rollup_device.argtypes = [vp, PS, PB, i32, vp, PR,
+                                                    vp]
+        lib.otsdb_agg_run_rollup_device.restype = C.c_int
+        lib.otsdb_agg_run_rollup.argtypes = [vp, PS, PB, i32, vp, PR]
+        lib.otsdb_agg_run_rollup.restype = C.c_int
     # bound only on the ABI it was added to: a stale library of another
     # version must not hand out a symbol of other arguments
     if lib.otsdb_abi_version() == 6 and hasattr(lib, "otsdb_sel_retarget"):

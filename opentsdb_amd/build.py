@@ -5,9 +5,10 @@ resulting .so travels to the GPU box with the repository snapshot.
 
 The device code is split over translation units compiled in parallel: the
 engine (host code, the non-template kernels and the aggregator-templated
-ones) and two units per downsampling monoid (csrc/ds_tu.hip with
+ones), two units per downsampling monoid (csrc/ds_tu.hip with
 -DOTSDB_DS_MONOID=n: the downsample / ordered-fold kernels of that monoid,
-and with -DOTSDB_DS_PART=1 the cells fold of that monoid).
+and with -DOTSDB_DS_PART=1 the cells fold of that monoid) and csrc/rollup.hip
+(the prep and ring kernels of the two rollup states, nothing else).
 """
 import glob
 import os
@@ -46,7 +47,9 @@ def up_to_date(out=OUT):
 def _units(out_dir, defines):
     d = ["-D" + x for x in defines]
     units = [(os.path.join(CSRC, "engine.hip"), d,
-              os.path.join(out_dir, "engine.o"))]
+              os.path.join(out_dir, "engine.o")),
+             (os.path.join(CSRC, "rollup.hip"), d,
+              os.path.join(out_dir, "rollup.o"))]
     # part 1 (the cells fold, cellfold.hip) first: its units are the longest
     for part in (1, 0):
         for m in range(N_DS_MONOIDS):
@@ -98,10 +101,12 @@ def build(force=False, verbose=False, jobs=None, defines=(), out=None):
             return True
         t = os.path.getmtime(obj)
         part1 = "-DOTSDB_DS_PART=1" in extra
-        ds = src.endswith("ds_tu.hip")
+        ds = src.endswith(("ds_tu.hip", "rollup.hip"))
         return any(os.path.getmtime(d) > t for d in DEPS
                    if (part1 or not d.endswith("cellfold.hip")) and
-                   not (ds and os.path.basename(d) in engine_only))
+                   not (ds and os.path.basename(d) in engine_only) and
+                   (src.endswith("rollup.hip") or
+                    not d.endswith("rollup.hip")))
 
     todo = [u for u in units if stale(u)]
     with ThreadPoolExecutor(jobs) as ex:

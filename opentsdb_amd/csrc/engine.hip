@@ -256,6 +256,10 @@ struct otsdb_ctx {
   int64_t tiles_chunk = 0;
   int64_t tiles_whole = 0;
   bool verbatim = false;  // run_raw_verbatim: the cells query's rows as stored
+  // a rollup call (otsdb_agg_run_rollup*, RollupScope): the rollup state its
+  // rows are built with and the points' value_count column (device)
+  RollupKind rollup = ROLLUP_NONE;
+  const int64_t* rollup_cnt = nullptr;
   // the cells fold's uniform kernel met a qualifier that is not its series'
   // (ERR_CELLS_NONUNI): this call's next attempt takes the general kernel
   bool cells_no_uni = false;
@@ -962,6 +966,15 @@ otsdb_status build_rows(otsdb_ctx* c, const otsdb_query_spec* spec,
       a.series_row = series_row;
       launch_ds<M>(DS_CELLS, a);
     });
+  } else if (c->rollup) {
+    // rollup avg / count (rollup.hip): the same prep and ring, the counts
+    // beside the batch
+    {
+      StageTimer tm(c, 3);
+      launch_rollup(c->rollup, DS_PREP, a, c->rollup_cnt);
+    }
+    StageTimer tm(c, 0);
+    launch_rollup(c->rollup, DS_RING, a, c->rollup_cnt);
   } else if (P.ds_sel) {
     // median / percentile downsampling: per-bucket selection
     {
@@ -1154,7 +1167,8 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
   const int64_t G = (int64_t)goff.size() - 1;
   const int64_t nb = P.nb;
   // chained partials continue each group's state in k_group (the row path)
-  bool fold = fold_path(spec, P, mode) && !ginit;
+  // (a rollup call's states exist only for the row path's prep and ring)
+  bool fold = fold_path(spec, P, mode) && !ginit && !c->rollup;
 
   // grid trimming for very wide windows (NONE fill only): the rows span only
   // the buckets that hold data
@@ -1352,7 +1366,8 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
     HIP_TRY(hipMemsetAsync(W.R.state, 0, (size_t)S * NB, st));
   // RateSpan inside k_bucketize (NONE fill; the FillingDownsampler's rate
   // origin and fill points stay with k_transform)
-  const bool rate_fused = P.sentinel && P.rate && !P.fill && !P.run_all;
+  const bool rate_fused =
+      P.sentinel && P.rate && !P.fill && !P.run_all && !c->rollup;
 
   bool ok = true;
   DsLaunch a = ds_args(c, P, B, W);
@@ -2019,6 +2034,73 @@ otsdb_status run_device_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   rc = compact(c, P, G, W.out_val, W.out_emit, W.counts, out);
   if (rc) return rc;
   return finish(c, G, out);
+}
+
+// ------------------------------------------------------- rollup queries
+// otsdb_agg_run_rollup*: the points are a rollup table's cells; R (the
+// rollup aggregator) and the downsampling function F pick how a bucket is
+// computed (Downsampler.java:162-228, FillingDownsampler.java:196-252;
+// DESIGN.md §4.3).
+struct Rollup {
+  int32_t agg;         // R, RollupQuery.getRollupAgg()
+  const int64_t* cnt;  // every point's valueCount()
+};
+
+// The checks that need no device, and the state the rows are built with
+// (ROLLUP_NONE: the ordinary F.runDouble — the single query, counts ignored).
+otsdb_status check_rollup(const otsdb_query_spec* s, const Rollup& r,
+                          RollupKind* kind) {
+  if (r.agg < 0 || r.agg >= OTSDB_AGG_COUNT_IDS)
+    return fail(OTSDB_E_NO_SUCH_ELEMENT, "No such aggregator: %d", r.agg);
+  otsdb_status rc = check_spec(s);
+  if (rc) return rc;
+  if (r.agg == OTSDB_AGG_DEV)
+    return fail(OTSDB_E_UNSUPPORTED,
+                "standard deviation over rolled up data is not supported");
+  if (!(s->ds_interval_ms > 0 || s->run_all))
+    return fail(OTSDB_E_UNSUPPORTED, "a rollup query without a downsampler");
+  if (s->n_cal_anchors > 0)
+    return fail(OTSDB_E_UNSUPPORTED,
+                "rollup queries over per-series calendar anchors");
+  *kind = ROLLUP_NONE;
+  if (r.agg == OTSDB_AGG_AVG) {
+    if (s->ds_agg_id != OTSDB_AGG_AVG)
+      return fail(OTSDB_E_UNSUPPORTED,
+                  "rollup avg downsampled with another function");
+    if (!r.cnt)
+      return fail(OTSDB_E_ILLEGAL_ARGUMENT, "rollup avg needs value_count");
+    *kind = ROLLUP_AVG;
+  } else if (s->ds_agg_id == OTSDB_AGG_COUNT) {
+    *kind = ROLLUP_COUNT;
+  }
+  return OTSDB_OK;
+}
+
+// the context's rollup state for one call, cleared on every exit path
+struct RollupScope {
+  otsdb_ctx* c;
+  RollupScope(otsdb_ctx* c_, RollupKind kind, const int64_t* cnt) : c(c_) {
+    c->rollup = kind;
+    c->rollup_cnt = kind == ROLLUP_AVG ? cnt : nullptr;
+  }
+  ~RollupScope() {
+    c->rollup = ROLLUP_NONE;
+    c->rollup_cnt = nullptr;
+  }
+};
+
+// device pointers throughout (r.cnt too)
+otsdb_status run_rollup_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
+                             const otsdb_batch* b, const Rollup& r,
+                             otsdb_result* out, std::vector<int64_t>& goff) {
+  RollupKind kind;
+  otsdb_status rc = check_rollup(spec, r, &kind);
+  if (rc) return rc;
+  if (kind == ROLLUP_AVG && (((uintptr_t)r.cnt) & 15) != 0)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT,
+                "value_count must be 16-byte aligned (16-B streaming loads)");
+  RollupScope scope(c, kind, r.cnt);
+  return run_device_impl(c, spec, b, out, goff);
 }
 
 // ----------------------------------- multi-aggregator and panel queries
@@ -4291,10 +4373,11 @@ otsdb_status otsdb_agg_run_cells_device(otsdb_ctx* c,
 
 // The host-pointer entries: the batch staged in HBM once, n results (q: the
 // multi-aggregator or panel request whose results `outs` are, null: one
-// single query).
+// single query; roll: that single query over rollup cells, roll->cnt on the
+// host and staged beside the batch when its state reads it).
 static otsdb_status run_host(otsdb_ctx* c, const otsdb_query_spec* spec,
                              const otsdb_batch* b, int n, otsdb_result* outs,
-                             const Req* q) {
+                             const Req* q, const Rollup* roll = nullptr) {
   CtxLock lk(c);
   HIP_TRY(hipSetDevice(c->device));
   std::vector<int64_t> goff;
@@ -4311,7 +4394,8 @@ static otsdb_status run_host(otsdb_ctx* c, const otsdb_query_spec* spec,
   // staging layout in HBM
   auto carve = [&](char* base) {
     Carve cv{base};
-    std::vector<void*> p(7 + 4 * (size_t)n);
+    std::vector<void*> p(8 + 4 * (size_t)n);
+    p[7 + 4 * n] = roll && roll->cnt ? cv.take<int64_t>(N + 1) : nullptr;
     p[0] = cv.take<int64_t>(S + 1);
     p[1] = cv.take<int64_t>(N + 1);
     p[2] = cv.take<int64_t>(N + 1);
@@ -4344,6 +4428,7 @@ static otsdb_status run_host(otsdb_ctx* c, const otsdb_query_spec* spec,
   if (b->series_float && (rc = h2d(pp[4], b->series_float, S))) return rc;
   if ((rc = h2d(pp[5], b->group_offsets, 8 * (G + 1)))) return rc;
   if ((rc = h2d(pp[6], b->group_members, 8 * M))) return rc;
+  if (roll && (rc = h2d(pp[7 + 4 * n], roll->cnt, 8 * N))) return rc;
   otsdb_batch db = *b;
   db.offsets = (const int64_t*)pp[0];
   db.ts_ms = (const int64_t*)pp[1];
@@ -4367,6 +4452,9 @@ static otsdb_status run_host(otsdb_ctx* c, const otsdb_query_spec* spec,
     dq.outs = dr.data();
     rc = dq.ds ? run_panel_impl(c, spec, dq, &db, goff)
                : run_multi_impl(c, spec, dq, &db, goff);
+  } else if (roll) {
+    const Rollup dro{roll->agg, (const int64_t*)pp[7 + 4 * n]};
+    rc = run_rollup_impl(c, spec, &db, dro, &dr[0], goff);
   } else {
     rc = run_device_impl(c, spec, &db, &dr[0], goff);
   }
@@ -4397,6 +4485,34 @@ otsdb_status otsdb_agg_run(otsdb_ctx* c, const otsdb_query_spec* spec,
                            const otsdb_batch* b, otsdb_result* out) {
   if (!c || !spec || !b || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
   return run_host(c, spec, b, 1, out, nullptr);
+}
+
+otsdb_status otsdb_agg_run_rollup_device(otsdb_ctx* c,
+                                         const otsdb_query_spec* spec,
+                                         const otsdb_batch* b,
+                                         int32_t rollup_agg_id,
+                                         const int64_t* value_count,
+                                         otsdb_result* out, void* hip_stream) {
+  if (!c || !spec || !b || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  const Rollup r{rollup_agg_id, value_count};
+  RollupKind kind;
+  const otsdb_status rc = check_rollup(spec, r, &kind);
+  if (rc) return rc;
+  DeviceCall dc(c, b, hip_stream);
+  return dc.rc ? dc.rc : run_rollup_impl(c, spec, b, r, out, dc.goff);
+}
+
+otsdb_status otsdb_agg_run_rollup(otsdb_ctx* c, const otsdb_query_spec* spec,
+                                  const otsdb_batch* b, int32_t rollup_agg_id,
+                                  const int64_t* value_count,
+                                  otsdb_result* out) {
+  if (!c || !spec || !b || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  Rollup r{rollup_agg_id, value_count};
+  RollupKind kind;
+  const otsdb_status rc = check_rollup(spec, r, &kind);
+  if (rc) return rc;
+  if (kind != ROLLUP_AVG) r.cnt = nullptr;  // ignored: nothing to stage
+  return run_host(c, spec, b, 1, out, nullptr, &r);
 }
 
 // otsdb_agg_plan_multi's bound of a call's workspace: the downsampler's rows

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "monoids.h"
+#include "rollup_monoids.h"
 
 namespace otsdb {
 

@@ -53,6 +53,23 @@ DEV double point_value(const BatchDev& B, int64_t i, int64_t bits, int sf) {
   const int f = B.is_float ? (int)B.is_float[i] : sf;
   return f ? bits_to_double(bits) : (double)bits;
 }
+// ... and of a rollup average's point, the count beside it (rollup_monoids.h)
+DEV RollPoint bits_to_double(RollBits b) {
+  return {bits_to_double(b.bits), b.cnt};
+}
+DEV RollPoint point_value(const BatchDev& B, int64_t i, RollBits b, int sf) {
+  return {point_value(B, i, b.bits, sf), b.cnt};
+}
+// point i as the operand of M's push, read from the batch (cnt: the points'
+// value_count column, read only for a state that takes it)
+template <class M>
+DEV auto point_operand(const BatchDev& B, const int64_t* cnt, int64_t i,
+                       int sf) {
+  typename PointBits<M>::type b{};
+  value_bits(b) = B.val[i];
+  load_count(b, cnt, i);
+  return point_value(B, i, b, sf);
+}
 
 // first index in [a, b) with ts >= t (the seek of Span.Iterator /
 // MockSeekableView on sorted points)
@@ -232,7 +249,8 @@ DEV int rates_beyond(const Params& P, int64_t t, double v, Next&& next,
 template <class M>
 DEV void prep_series(const Params& P, const BatchDev& B, SeriesMeta SM,
                      int* err_word, int64_t s, bool full, bool* keep_o,
-                     int64_t* lo_o, int64_t* hi_o) {
+                     int64_t* lo_o, int64_t* hi_o,
+                     const int64_t* cnt = nullptr) {
   const int64_t p0 = B.offsets[s], p1 = B.offsets[s + 1];
   const bool keep = p1 > p0 && B.ts[p0] <= P.end_ms && B.ts[p1 - 1] >= P.start_ms;
   int64_t lo = p1, hi = p1;
@@ -269,7 +287,7 @@ DEV void prep_series(const Params& P, const BatchDev& B, SeriesMeta SM,
       M st = M::init();
       int64_t i = hi;
       for (; i < p1 && B.ts[i] < e; ++i)
-        st.push(point_value(B, i, B.val[i], sf));
+        st.push(point_operand<M>(B, cnt, i, sf));
       int err = 0;
       of_val = st.finish(&err);
       of_has = 1;
@@ -292,7 +310,7 @@ DEV void prep_series(const Params& P, const BatchDev& B, SeriesMeta SM,
           }
           M b = M::init();
           for (; i < p1 && B.ts[i] < be; ++i)
-            b.push(point_value(B, i, B.val[i], sf));
+            b.push(point_operand<M>(B, cnt, i, sf));
           int e2 = 0;
           *tn = bt;
           *vn = b.finish(&e2);
@@ -617,9 +635,9 @@ DEV void sink_flush(SK& S, int64_t& flushed, int64_t limit,
 // nv < K: only the first nv points are in range (the step reaches past the
 // end of the series / window); nv == 0 leaves the lane empty (nseg = 0).
 template <class M, int K, bool FLOATONLY, class TT = int64_t,
-          class SK = RowSink>
+          class SK = RowSink, class VT = int64_t>
 DEV bool fold_fast(const Params& P, const BatchDev& B, int sf, int64_t i0,
-                   const TT* t, const int64_t* v, SK& S, int& err,
+                   const TT* t, const VT* v, SK& S, int& err,
                    int& nseg, int& cur_key, int& head_key, M& cur, M& head,
                    int nv = K) {
   if (nv <= 0) {
@@ -646,7 +664,7 @@ DEV bool fold_fast(const Params& P, const BatchDev& B, int sf, int64_t i0,
     // points): two runs, head and tail
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-      const double x =
+      const auto x =
           FLOATONLY ? bits_to_double(v[j]) : point_value(B, i0 + j, v[j], sf);
       const bool vj = j < nv;
       const bool inh = vj && t[j] < b_tail;
@@ -656,7 +674,7 @@ DEV bool fold_fast(const Params& P, const BatchDev& B, int sf, int64_t i0,
   } else {
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-      const double x =
+      const auto x =
           FLOATONLY ? bits_to_double(v[j]) : point_value(B, i0 + j, v[j], sf);
       const bool vj = j < nv;
       const bool inh = vj && t[j] < b_mid;
@@ -685,9 +703,9 @@ DEV bool fold_fast(const Params& P, const BatchDev& B, int sf, int64_t i0,
 // from the previous lane) goes to `head`, the last run (which may continue
 // into the next lane) stays in `cur`, runs in between close here.
 template <class M, int K, bool FLOATONLY, bool CHECKED, class TT = int64_t,
-          class SK = RowSink>
+          class SK = RowSink, class VT = int64_t>
 DEV void fold_lane(const Params& P, const BatchDev& B, int sf, int64_t i0,
-                   int64_t lo, int64_t hi, const TT* t, const int64_t* v,
+                   int64_t lo, int64_t hi, const TT* t, const VT* v,
                    SK& S, int& err, int& nseg,
                    int& cur_key, int& head_key, M& cur, M& head) {
   TT bnd = tmin<TT>();  // first timestamp past cur_key's bucket
@@ -700,7 +718,7 @@ DEV void fold_lane(const Params& P, const BatchDev& B, int sf, int64_t i0,
       k = (int)tbucket(P, t[j]);
       bnd = tbound(P, (int64_t)k + 1, TT{});
     }
-    const double x = FLOATONLY ? bits_to_double(v[j]) : point_value(B, i, v[j], sf);
+    const auto x = FLOATONLY ? bits_to_double(v[j]) : point_value(B, i, v[j], sf);
     if (nseg == 0) {
       cur_key = k;
       cur = M::from(x);
@@ -752,8 +770,8 @@ DEV void seg_scan_dpp(int key, M& st) {
 // predecessor's final state.  Lane 0's predecessor is the previous step's
 // open bucket (the carry).  Cost: (longest chain + 1) x K pushes per step
 // (a 5 m bucket of 10 s points spans <= 3 whole lanes).
-template <class M, int K>
-DEV M push_run(M st, const BatchDev& B, int sf, int64_t i0, const int64_t* v,
+template <class M, int K, class VT = int64_t>
+DEV M push_run(M st, const BatchDev& B, int sf, int64_t i0, const VT* v,
                uint32_t mask) {
 #pragma unroll
   for (int j = 0; j < K; ++j)
@@ -823,10 +841,10 @@ DEV void ordered_step(const Params& P, const BatchDev& B, int sf, int64_t lo,
 // value to its double bits): the per-point type tests and their registers
 // are not compiled in
 template <class M, int K, int DPP, class TT = int64_t, int FO = 0,
-          class SK = RowSink>
+          class SK = RowSink, class VT = int64_t>
 DEV void reduce_step(const Params& P, const BatchDev& B, int sf, int64_t lo,
                      int64_t hi, int64_t base, int64_t i0, const TT* t,
-                     const int64_t* v, SK& S, int& err,
+                     const VT* v, SK& S, int& err,
                      int& carry_key, M& carry, bool keep_open = false) {
   constexpr int PTS = 64 * K;
   const int lane = LANE;
@@ -1118,7 +1136,8 @@ DEV void rate_finish(const Params& P, const SeriesMeta& SM, int64_t s,
 template <class M, int K, int PF, int NT, int ABL, int DPP, int WIN, int FL,
           int RATE, class SK = RowSink>
 DEV void bucketize_series(const Params& P, const BatchDev& B,
-                          const SeriesMeta& SM, SK& S, int64_t s) {
+                          const SeriesMeta& SM, SK& S, int64_t s,
+                          const int64_t* cnt = nullptr) {
   static_assert(K % 2 == 0, "K must be even (16-byte loads)");
   static_assert((WIN & (WIN - 1)) == 0, "WIN: power of two");
   static_assert(!RATE || WIN > 0, "RATE needs the ring");
@@ -1144,8 +1163,10 @@ DEV void bucketize_series(const Params& P, const BatchDev& B,
   int carry_key = INT32_MIN;
   M carry = M::init();
   constexpr int PTS = 64 * K;
-  // K consecutive points of this lane: K/2 16-byte loads per column
-  auto load_step = [&](int64_t i0, int64_t* t, int64_t* v) {
+  // K consecutive points of this lane: K/2 16-byte loads per column (the
+  // rollup average's counts are a third column, rollup_monoids.h)
+  using VT = typename PointBits<M>::type;
+  auto load_step = [&](int64_t i0, int64_t* t, VT* v) {
     if (i0 + K <= hi) {
 #pragma unroll
       for (int j = 0; j < K; j += 2) {
@@ -1160,23 +1181,27 @@ DEV void bucketize_series(const Params& P, const BatchDev& B,
           vv = *pv;
         }
         t[j] = tt.x; t[j + 1] = tt.y;
-        v[j] = vv.x; v[j + 1] = vv.y;
+        value_bits(v[j]) = vv.x; value_bits(v[j + 1]) = vv.y;
+        load_count2(v[j], v[j + 1], cnt, i0 + j);
       }
     } else {
 #pragma unroll
       for (int j = 0; j < K; ++j) {
         t[j] = (i0 + j < hi) ? B.ts[i0 + j] : 0;
-        v[j] = (i0 + j < hi) ? B.val[i0 + j] : 0;
+        value_bits(v[j]) = (i0 + j < hi) ? B.val[i0 + j] : 0;
+        load_count_if(i0 + j < hi, v[j], cnt, i0 + j);
       }
     }
   };
-  int64_t tn[K], vn[K];
+  int64_t tn[K];
+  VT vn[K];
   const int64_t base0 = lo & ~(int64_t)1;
   if (PF) load_step(base0 + (int64_t)K * lane, tn, vn);
   L2Touch pt_, pv_;
   for (int64_t base = base0; base < hi; base += PTS) {
     const int64_t i0 = base + (int64_t)K * lane;
-    int64_t t[K], v[K];
+    int64_t t[K];
+    VT v[K];
     if (PF) {
 #pragma unroll
       for (int j = 0; j < K; ++j) { t[j] = tn[j]; v[j] = vn[j]; }

@@ -196,4 +196,15 @@ bool launch_ds(DsKernel k, const DsLaunch& a);
 template <class M>
 bool launch_cells(DsKernel k, const DsLaunch& a);
 
+// Rollup queries (rollup.hip): DS_PREP and DS_RING over a
+// rollup downsampling state, the points' value_count column beside the batch
+// (device pointer; read by ROLLUP_AVG only).  No other kernel exists for them.
+enum RollupKind {
+  ROLLUP_NONE = 0,  // the ordinary downsampling function
+  ROLLUP_AVG,       // sum of sum cells / sum of count cells (MRollAvg)
+  ROLLUP_COUNT      // sum of count cells (MRollCount)
+};
+bool launch_rollup(RollupKind kind, DsKernel k, const DsLaunch& a,
+                   const int64_t* value_count);
+
 }  // namespace otsdb

@@ -16,7 +16,7 @@ import numpy as np
 from . import abi
 from .core import (Aggregator, Aggregators, IllegalArgumentException,
                    IllegalStateException, NoSuchElementException,
-                   raise_for_status)
+                   UnsupportedOperationException, raise_for_status)
 
 
 class DataPoint:
@@ -154,6 +154,36 @@ def panel_args(queries):
     return n, ds, ids, it
 
 
+def rollup_args(spec, rollup_agg, value_count):
+    """The rollup arguments of a rollup call as the C-ABI takes them:
+    (rollup aggregator id, int64 counts or None).  `rollup_agg`: the rollup
+    table's aggregator (RollupQuery.getRollupAgg) as multi_args takes
+    aggregators; `value_count`: every point's valueCount(), required when the
+    rollup aggregator is avg.  Checked before anything touches the device."""
+    _, ids, _ = multi_args([rollup_agg])
+    r = int(ids[0])
+    if r not in Aggregators._by_id:
+        raise NoSuchElementException("No such aggregator: %d" % r)
+    if r == Aggregators.DEV.id:
+        raise UnsupportedOperationException(
+            "standard deviation over rolled up data is not supported")
+    if not (spec.ds_interval_ms > 0 or spec.run_all):
+        raise UnsupportedOperationException(
+            "a rollup query downsamples: raw group-by is not supported")
+    if spec.n_cal_anchors > 0:
+        raise UnsupportedOperationException(
+            "rollup queries over per-series calendar anchors are not supported")
+    if r != Aggregators.AVG.id:
+        return r, None  # the counts are ignored
+    if spec.ds_agg_id != Aggregators.AVG.id:
+        raise UnsupportedOperationException(
+            "rollup avg downsampled with another function is not supported")
+    if value_count is None:
+        raise IllegalArgumentException(
+            "a rollup avg query needs every point's value_count")
+    return r, value_count
+
+
 def _host_results(n, G, cap):
     """n host results of capacity `cap` for G groups: the abi.Result array
     and a function that slices them into one list of DataPoints (one per
@@ -266,6 +296,29 @@ class Engine:
         return [DataPoints(ts[offs[g]:offs[g + 1]], bits[offs[g]:offs[g + 1]],
                            isint[offs[g]:offs[g + 1]]) for g in range(G)]
 
+    def run_rollup(self, spec, batch, rollup_agg, value_count=None):
+        """A query over rollup-table points (host arrays): `batch` holds the
+        rollup cells' values, `rollup_agg` is the table's aggregator and
+        `value_count[i]` point i's valueCount().  Rollup avg downsampled with
+        avg is sum of sums / sum of counts; any other rollup aggregator (dev
+        aside) downsampled with count sums the cells; every other pair is
+        what run() gives.  Results as run()'s."""
+        r, vc = rollup_args(spec, rollup_agg, value_count)
+        n = int(batch.offsets[-1]) if len(batch.offsets) else 0
+        if vc is not None:
+            vc = np.ascontiguousarray(vc, dtype=np.int64)
+            if vc.shape != (n,):
+                raise IllegalArgumentException(
+                    "value_count has %s entries for %d points"
+                    % (vc.shape, n))
+        sz = self.plan(spec, batch)
+        rs, points = _host_results(1, batch.n_groups,
+                                   max(1, int(sz.max_out_points)))
+        b = batch.as_abi()
+        self._check(self.lib.otsdb_agg_run_rollup(
+            self.ctx, C.byref(spec), C.byref(b), r,
+            None if vc is None else vc.ctypes.data, rs))
+        return points()[0]
 
     def plan_multi(self, spec, aggs, batch, interps=None):
         n, ids, it = multi_args(aggs, interps)
@@ -448,6 +501,25 @@ def run_device(engine, spec, dbatch, dresult, stream=None):
     engine._check(engine.lib.otsdb_agg_run_device(
         engine.ctx, C.byref(spec), C.byref(b), C.byref(r),
         None if stream is None else C.c_void_p(stream)))
+
+
+def run_rollup_device(engine, spec, dbatch, rollup_agg, dcount, dresult,
+                      stream=None):
+    """Device-resident rollup call (Engine.run_rollup's semantics): `dcount`
+    is an int64 tensor of every point's valueCount() beside dbatch's columns
+    (16-byte aligned like them), or None when the rollup aggregator is not
+    avg."""
+    r, vc = rollup_args(spec, rollup_agg, dcount)
+    if vc is not None and vc.numel() != dbatch.ts.numel():
+        raise IllegalArgumentException(
+            "value_count has %d entries for %d points"
+            % (vc.numel(), dbatch.ts.numel()))
+    b = _abi_cached(dbatch, _BATCH_TENSORS, dbatch.as_abi,
+                    dbatch.group_offsets._version)
+    res = _abi_cached(dresult, _RESULT_TENSORS, dresult.as_abi, dresult.cap)
+    engine._check(engine.lib.otsdb_agg_run_rollup_device(
+        engine.ctx, C.byref(spec), C.byref(b), r,
+        None if vc is None else vc.data_ptr(), C.byref(res), _stream(stream)))
 
 
 def _fold_spec(spec, fold, bit=None):
