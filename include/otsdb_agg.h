@@ -253,7 +253,10 @@ typedef struct {
 
 typedef struct {
   int64_t n_buckets;        /* grid buckets per series (downsampled path)  */
-  int64_t max_out_points;   /* upper bound of total output points          */
+  int64_t max_out_points;   /* upper bound of total output points: groups x
+                             * buckets; n_points on the raw path (each span
+                             * in one group); groups x n_points for a
+                             * NONE-fill window past 4e9 series x buckets    */
   int64_t workspace_bytes;  /* device scratch this query needs              */
 } otsdb_sizes;
 

@@ -4347,6 +4347,15 @@ otsdb_status otsdb_agg_plan(otsdb_ctx* c, const otsdb_query_spec* spec,
   }
   out->n_buckets = P.nb;
   out->max_out_points = b->n_groups * P.nb;
+  // Under NONE fill a group emits only at buckets its members have points in:
+  // at most n_points per group, whatever the grid and however many groups a
+  // series is listed in.  The bound holds for every NONE-fill grid; it is
+  // applied past 4e9 series x buckets, where groups x buckets of the window
+  // as given is no size a caller can allocate (the host entries stage their
+  // results by it), and every smaller plan stays as it was.
+  if (!P.run_all && !P.fill && (double)b->n_series * (double)P.nb > 4.0e9)
+    out->max_out_points =
+        std::min(out->max_out_points, b->n_groups * b->n_points);
   out->workspace_bytes =
       b->n_series * (P.nb * 9 + 48) + b->n_groups * (P.nb * 9 + 8);
   return OTSDB_OK;

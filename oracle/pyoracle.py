@@ -102,13 +102,20 @@ def view_stream(spec, ts, bits, is_float, seek=None):
     bits = np.ascontiguousarray(bits, np.int64)
     isf = np.ascontiguousarray(is_float, np.uint8)
     cap = 4 * len(ts) + 1024
-    out = np.zeros(cap, POINT)
     need = C.c_int64(0)
     err = C.create_string_buffer(256)
-    st = l.or_view_stream(C.byref(spec), 0 if seek is None else 1,
-                          0 if seek is None else int(seek), len(ts),
-                          ts.ctypes.data, bits.ctypes.data, isf.ctypes.data,
-                          out.ctypes.data, cap, C.byref(need), err, 256)
+    while True:
+        out = np.zeros(cap, POINT)
+        st = l.or_view_stream(C.byref(spec), 0 if seek is None else 1,
+                              0 if seek is None else int(seek), len(ts),
+                              ts.ctypes.data, bits.ctypes.data,
+                              isf.ctypes.data, out.ctypes.data, cap,
+                              C.byref(need), err, 256)
+        if st == 7 and need.value > cap:
+            # a filling grid of many more buckets than the series has points
+            cap = need.value
+            continue
+        break
     if st != 0:
         raise OracleError(st, err.value.decode())
     return out[:need.value].copy()

@@ -83,10 +83,12 @@ class Checker:
 
     def __init__(self, engine, batch):
         self.engine, self.batch, self.views = engine, batch, {}
+        self.got = None  # the engine's result of the last accepted query
 
     def __call__(self, spec, exact, where, key=None, blind=False,
                  may_reject=False):
         got, ref = run_both(self.engine, spec, self.batch)
+        self.got = got
         if ref is None:  # both sides reject the query: status parity
             assert may_reject, where + ": rejected by the reference"
             return None
@@ -99,7 +101,7 @@ class Checker:
                     self.views[key] = views
             floor = contribution_floor(spec, self.batch, ref, views)
         if blind:
-            got = zero_sign_blind(got, ref)
+            self.got = got = zero_sign_blind(got, ref)
         compare(got, ref, exact, where, floor)
         return ref
 

@@ -85,6 +85,51 @@ def test_argument_checks_reach_no_device(lib):
     assert sz.workspace_bytes > single.workspace_bytes
 
 
+def test_plan_bounds_a_very_wide_none_window_by_its_points(lib):
+    """Past 4e9 series x buckets a NONE-fill window is planned by what it can
+    emit, groups x n_points (a group emits only at buckets its members have
+    points in), not by groups x buckets of the window as given: the host
+    entries stage their results by this figure.  A fill policy emits every
+    bucket, and smaller windows keep groups x buckets."""
+    b = abi.Batch()
+    b.n_series, b.n_points, b.n_groups = 43, 100000, 3
+    hour = 3600000
+
+    def sizes(fill, end, entry="single"):
+        spec = core.make_spec(0, end, core.Aggregators.get("sum"),
+                              core.DownsamplingSpecification("1h-avg-" + fill),
+                              0, end)
+        sz = abi.Sizes()
+        if entry == "single":
+            st = lib.otsdb_agg_plan(None, C.byref(spec), C.byref(b),
+                                    C.byref(sz))
+        else:
+            ids = np.array([0, 3], np.int32)
+            it = np.full(2, -1, np.int32)
+            st = lib.otsdb_agg_plan_multi(None, C.byref(spec), 2,
+                                          ids.ctypes.data, it.ctypes.data,
+                                          C.byref(b), C.byref(sz))
+        assert st == abi.OK
+        return sz
+    end = core.LONG_MAX // 2
+    for entry in ("single", "multi"):
+        sz = sizes("none", end, entry)
+        assert sz.n_buckets == end // hour + 1
+        assert 43 * sz.n_buckets > 4e9
+        assert sz.max_out_points == 3 * 100000, entry
+    # the largest NONE window at or below 4e9 series x buckets, and the next
+    nb = int(4e9) // 43
+    assert sizes("none", nb * hour - 1).max_out_points == 3 * nb
+    assert sizes("none", (nb + 1) * hour - 1).max_out_points == 3 * 100000
+    # few points: groups x buckets where that is the smaller
+    b.n_points = 10**13
+    sz = sizes("none", (nb + 1) * hour - 1)
+    assert sz.max_out_points == 3 * (nb + 1)
+    b.n_points = 100000
+    sz = sizes("nan", 10**8 * hour)  # a fill policy emits every bucket
+    assert sz.n_buckets == 10**8 and sz.max_out_points == 3 * 10**8
+
+
 def test_multi_args():
     n, ids, it = multi_args(["min", core.Aggregators.get("avg"), 3, "p99"])
     assert n == 4 and ids.dtype == np.int32 and it.dtype == np.int32
