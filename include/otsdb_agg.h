@@ -314,7 +314,8 @@ otsdb_status otsdb_agg_run_device(otsdb_ctx* ctx, const otsdb_query_spec* spec,
  * single query's over these bucket values.
  * value_count[i] is point i's valueCount() (RollupSeq.java:659-679) — the
  * (sum, count) pairs RollupSeq's iterator yields after its sync(): pairing
- * sum and count cells stays with the caller.  Required when R = avg (NULL:
+ * sum and count cells stays with the caller here (otsdb_agg_run_rollup_rows*
+ * below takes the cells themselves).  Required when R = avg (NULL:
  * OTSDB_E_ILLEGAL_ARGUMENT; 16-byte aligned like ts_ms / val on the device
  * entry), otherwise ignored and may be NULL.
  * A spec without a downsampler (ds_interval_ms == 0 and no run_all) or with
@@ -808,12 +809,99 @@ otsdb_status otsdb_agg_run_raw(otsdb_ctx* ctx, const otsdb_query_spec* spec,
                                const otsdb_raw_rows* raw, int32_t fix_duplicates,
                                const otsdb_batch* batch, otsdb_result* out);
 
+/* ---- rollup queries from storage rows ----------------------------------- */
+/* The rows of a ROLLUP table as the scanner delivers them (otsdb_raw_rows:
+ * one entry per (series, rollup row); rollup cells are never compacted,
+ * SaltScanner.java:765-809, so a column is one cell), paired and decoded on
+ * the device in place of RollupSpan.addRow (RollupSpan.java:55-72),
+ * RollupSeq.setRow / addRow / append (RollupSeq.java:126-322) and
+ * RollupIterator's sync() / seek() / value / valueCount() decode (:515-745)
+ * under Span.seekRow / Span.Iterator (Span.java:360-471).                    */
+typedef struct {
+  int32_t interval_s;     /* RollupInterval.getIntervalSeconds()              */
+  int32_t value_id;       /* RollupConfig id of the value cells' aggregator
+                             ("sum" when R = avg), 0..127                     */
+  int32_t count_id;       /* id of "count"; read only when R = avg            */
+  int32_t fix_duplicates; /* tsd.storage.fix_duplicates                       */
+} otsdb_rollup_table;
+
+/* Decode only, otsdb_decode_cells_device's contract (DEVICE pointers;
+ * ts_ms = NULL only counts: offsets filled, offsets[S] = points).  With
+ * R = rollup_agg_id:
+ *  - R = avg, the tests in this order: qual[0] & 0x7F == value_id: a value
+ *    cell; == count_id: a count cell; a qualifier starting with the 3 bytes
+ *    "sum": a value cell, old style, 4 bytes stripped; with the 5 bytes
+ *    "count": a count cell, 6 stripped (the byte after the name is not
+ *    compared, as in the reference: "sumX" passes for "sum:").  Otherwise:
+ *    the id, or a qualifier starting with "<R>:" (R's name in lowercase, the
+ *    colon compared), stripped.  The 2 bytes after the id / stripped bytes
+ *    are offset << 4 | flags.  Any other cell, or one too short:
+ *    OTSDB_E_ILLEGAL_DATA (RollupSeq.java:136-161);
+ *  - consecutive rows of one series and base time are one RollupSeq; base
+ *    times that do not otherwise increase strictly inside a series:
+ *    OTSDB_E_UNSUPPORTED (the scanner delivers key order);
+ *  - per kind, an offset below the last accepted one, or equal to it without
+ *    fix_duplicates: OTSDB_E_ILLEGAL_DATA for a value cell,
+ *    OTSDB_E_ILLEGAL_ARGUMENT for a count cell; with fix_duplicates a cell
+ *    whose col_ts is older than the last accepted one's is skipped, any other
+ *    replaces it (col_ts = NULL: each later duplicate replaces)
+ *    (RollupSeq.java:217-322);
+ *  - ts_ms = base_s * 1000 + offset * interval_s * 1000; val / is_float as
+ *    Internal.extractIntegerValue / extractFloatingPointValue;
+ *  - R = avg: the points are the value cells that have a count cell of the
+ *    same offset, value_count that cell's value ((long) of a float one: NaN
+ *    is 0, saturating); otherwise every accepted value cell is a point and
+ *    value_count is not written (may be NULL);
+ *  - seek_ms (R = avg; INT64_MIN: none; always milliseconds): the timestamp
+ *    the query's downsampler hands its source.  In the row Span.seekRow picks
+ *    (the first whose last paired point is >= seek_ms, else the series' last)
+ *    the points from seek_ms on are what RollupIterator.seek leaves: value
+ *    cells [i0 + k:] paired with count cells [j0 + k:], (i0, j0) the row's
+ *    first pair and k its value cells from i0 on before seek_ms — unpaired
+ *    cells before the seek point can drop later pairs.  The pairs before
+ *    seek_ms are emitted unchanged.
+ * Deviations: an offset field >= 3840 (first qualifier byte 0xF0..0xFF) is
+ * the millisecond form, which the reference reads past the 2 bytes
+ * (RollupUtils.java:213-215): OTSDB_E_UNSUPPORTED.  Value bytes whose length
+ * is not the qualifier's, or is none of 1/2/4/8 (a float's 4/8), which the
+ * reference appends unchecked and reads misaligned: OTSDB_E_ILLEGAL_DATA.  A
+ * row of more than 8,192 columns, or a RollupSeq of more than 65,535:
+ * OTSDB_E_UNSUPPORTED.  The first failing row in row order, and the first
+ * failing column in it, decides the status.  raw / table NULL or
+ * interval_s <= 0: OTSDB_E_ILLEGAL_ARGUMENT; an unknown rollup_agg_id:
+ * OTSDB_E_NO_SUCH_ELEMENT; dev: OTSDB_E_UNSUPPORTED.                         */
+otsdb_status otsdb_rollup_decode_rows_device(
+    otsdb_ctx* ctx, const otsdb_raw_rows* raw, const otsdb_rollup_table* table,
+    int32_t rollup_agg_id, int64_t n_series, int64_t seek_ms, int64_t* offsets,
+    int64_t* ts_ms, int64_t* val, uint8_t* is_float, int64_t* value_count,
+    int64_t capacity, void* hip_stream);
+
+/* The rollup query from the rows: the decode above into a context-owned
+ * buffer, then exactly what otsdb_agg_run_rollup_device runs on those columns
+ * (the same refusals: R = dev, R = avg with F != avg, no downsampler,
+ * per-series calendar anchors).  `batch` supplies n_series and the groups
+ * only.  seek_ms is derived from the spec as Downsampler.seekInterval does
+ * (Downsampler.java:412-434): start_ms for "all", the first calendar edge at
+ * or after start_ms, else start_ms rounded up to a multiple of the interval.
+ * _device: DEVICE pointers; otsdb_agg_run_rollup_rows: HOST pointers,
+ * synchronous, otsdb_agg_run's OTSDB_E_CAPACITY contract.                    */
+otsdb_status otsdb_agg_run_rollup_rows_device(
+    otsdb_ctx* ctx, const otsdb_query_spec* spec, const otsdb_raw_rows* raw,
+    const otsdb_rollup_table* table, int32_t rollup_agg_id,
+    const otsdb_batch* batch, otsdb_result* out, void* hip_stream);
+otsdb_status otsdb_agg_run_rollup_rows(
+    otsdb_ctx* ctx, const otsdb_query_spec* spec, const otsdb_raw_rows* raw,
+    const otsdb_rollup_table* table, int32_t rollup_agg_id,
+    const otsdb_batch* batch, otsdb_result* out);
+
 /* ---- stage timing (bench roofline) ------------------------------------- */
 /* When enabled, every query records HIP events around its pipeline stages
  * on the query's stream.  otsdb_prof_read returns, per stage, the summed
  * milliseconds and the number of launches since the last reset:
  * [0] k_bucketize  [1] k_transform  [2] k_group+k_combine  [3] k_prep
- * [4] k_compact+k_scan.  Synchronises the stream.                           */
+ * [4] k_compact+k_scan; [5] query-time compaction, [6] span assembly, [7] the
+ * decode into the context's columnar buffer (compacted cells, rollup rows).
+ * Synchronises the stream.                                                  */
 otsdb_status otsdb_prof_enable(otsdb_ctx* ctx, int enable);
 otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
                              int n, int reset);

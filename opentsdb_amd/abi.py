@@ -121,6 +121,17 @@ class RawRows(C.Structure):
     ]
 
 
+class RollupTable(C.Structure):
+    """otsdb_rollup_table: the rollup interval, the RollupConfig ids of the
+    value and count cells, tsd.storage.fix_duplicates."""
+    _fields_ = [
+        ("interval_s", C.c_int32),
+        ("value_id", C.c_int32),
+        ("count_id", C.c_int32),
+        ("fix_duplicates", C.c_int32),
+    ]
+
+
 class GenSpec(C.Structure):
     _fields_ = [
         ("seed", C.c_uint64),
@@ -159,6 +170,8 @@ EXPORTS = [
     "otsdb_agg_plan_panel", "otsdb_agg_run_panel_device",
     "otsdb_agg_run_panel", "otsdb_agg_run_cells_panel_device",
     "otsdb_agg_run_rollup_device", "otsdb_agg_run_rollup",
+    "otsdb_rollup_decode_rows_device", "otsdb_agg_run_rollup_rows_device",
+    "otsdb_agg_run_rollup_rows",
 ]
 
 MULTI_MAX = 32  # OTSDB_MULTI_MAX
@@ -298,6 +311,20 @@ def load(path=None):
         lib.otsdb_agg_run_rollup_device.restype = C.c_int
         lib.otsdb_agg_run_rollup.argtypes = [vp, PS, PB, i32, vp, PR]
         lib.otsdb_agg_run_rollup.restype = C.c_int
+    # rollup queries from storage rows: (ctx, raw, table, rollup_agg_id,
+    # n_series, seek_ms, offsets, ts_ms, val, is_float, value_count,
+    # capacity, stream) and (ctx, spec, raw, table, rollup_agg_id, batch,
+    # result [, stream])
+    if hasattr(lib, "otsdb_agg_run_rollup_rows"):
+        PT = C.POINTER(RollupTable)
+        lib.otsdb_rollup_decode_rows_device.argtypes = [
+            vp, PW, PT, i32, i64, i64, vp, vp, vp, vp, vp, i64, vp]
+        lib.otsdb_rollup_decode_rows_device.restype = C.c_int
+        lib.otsdb_agg_run_rollup_rows_device.argtypes = [vp, PS, PW, PT, i32,
+                                                         PB, PR, vp]
+        lib.otsdb_agg_run_rollup_rows_device.restype = C.c_int
+        lib.otsdb_agg_run_rollup_rows.argtypes = [vp, PS, PW, PT, i32, PB, PR]
+        lib.otsdb_agg_run_rollup_rows.restype = C.c_int
     # bound only on the ABI it was added to: a stale library of another
     # version must not hand out a symbol of other arguments
     if lib.otsdb_abi_version() == 6 and hasattr(lib, "otsdb_sel_retarget"):

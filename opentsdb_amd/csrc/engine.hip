@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -29,6 +30,7 @@
 #include "decode.hip"
 #include "raw.hip"
 #include "rows.hip"
+#include "rollup_rows.hip"
 #include "calendar.hip"
 #include "multi.hip"
 #include "panel.hip"
@@ -2101,6 +2103,204 @@ otsdb_status run_rollup_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
                 "value_count must be 16-byte aligned (16-B streaming loads)");
   RollupScope scope(c, kind, r.cnt);
   return run_device_impl(c, spec, b, out, goff);
+}
+
+// ------------------------------------------ rollup queries from storage rows
+// otsdb_rollup_decode_rows_device / otsdb_agg_run_rollup_rows*: the rows of a
+// rollup table paired and decoded on the device (rollup_rows.hip, DESIGN.md
+// §4.3.1).
+otsdb_status check_rollup_table(const otsdb_raw_rows* raw,
+                                const otsdb_rollup_table* t, int32_t agg) {
+  if (!raw || !t) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  if (agg < 0 || agg >= OTSDB_AGG_COUNT_IDS)
+    return fail(OTSDB_E_NO_SUCH_ELEMENT, "No such aggregator: %d", agg);
+  if (agg == OTSDB_AGG_DEV)
+    return fail(OTSDB_E_UNSUPPORTED,
+                "standard deviation over rolled up data is not supported");
+  if (t->interval_s <= 0)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "rollup interval %d s", t->interval_s);
+  const bool avg = agg == OTSDB_AGG_AVG;
+  if (t->value_id < 0 || t->value_id > 127 ||
+      (avg && (t->count_id < 0 || t->count_id > 127)))
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "rollup aggregator ids are 0..127");
+  if (raw->n_rows < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative n_rows");
+  if (!raw->row_series || !raw->row_base_s || !raw->row_col_off ||
+      !raw->col_qual_off || !raw->col_val_off ||
+      (raw->n_rows > 0 && (!raw->qual || !raw->val)))
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null raw row array");
+  return OTSDB_OK;
+}
+
+// The decode without the lock (the contract of decode_impl: ts_ms null only
+// counts).  cnt may be null (R not avg: never written).
+otsdb_status rollup_decode_impl(otsdb_ctx* c, const otsdb_raw_rows* raw,
+                                const otsdb_rollup_table* t, int32_t agg,
+                                int64_t n_series, int64_t seek_ms,
+                                int64_t* offsets, int64_t* ts_ms, int64_t* val,
+                                uint8_t* is_float, int64_t* cnt,
+                                int64_t capacity, hipStream_t st,
+                                bool counted = false) {
+  const int64_t R = raw->n_rows, S = n_series;
+  if (S < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
+  RollupRowsDev T{};
+  T.R = R;
+  T.row_series = raw->row_series;
+  T.row_base_s = raw->row_base_s;
+  T.row_col_off = raw->row_col_off;
+  T.col_qoff = raw->col_qual_off;
+  T.qual = raw->qual;
+  T.col_voff = raw->col_val_off;
+  T.val = raw->val;
+  T.col_ts = raw->col_ts;
+  T.interval_ms = (int64_t)t->interval_s * 1000;
+  T.seek_ms = seek_ms;
+  T.need_count = agg == OTSDB_AGG_AVG;
+  T.value_id = t->value_id;
+  T.count_id = t->count_id;
+  T.fix = t->fix_duplicates != 0;
+  // RollupUtils.getRollupQualifierPrefix(R.toString()): lowercase + ':'
+  const char* name = kAggs[agg].name;
+  int pl = 0;
+  for (; name[pl] && pl < (int)sizeof(T.prefix) - 1; ++pl)
+    T.prefix[pl] = (uint8_t)tolower((unsigned char)name[pl]);
+  T.prefix[pl++] = ':';
+  T.prefix_len = pl;
+  const bool seek = T.need_count && seek_ms != INT64_MIN;
+  // workspace: row counts, row output offsets, last paired timestamps, the
+  // sought marks, the first error, the scan's temporary storage
+  const size_t tmpb = scan_tmp_bytes(R, st);
+  const size_t A = ((size_t)(R + 1) * 8 + 255) & ~(size_t)255;
+  otsdb_status rc = ensure(&c->dec_ws, &c->dec_ws_cap, 4 * A + 256 + tmpb);
+  if (rc) return rc;
+  char* w = (char*)c->dec_ws;
+  int64_t* row_count = (int64_t*)w;
+  int64_t* row_out = (int64_t*)(w + A);
+  int64_t* row_last = (int64_t*)(w + 2 * A);
+  uint8_t* sought = (uint8_t*)(w + 3 * A);
+  unsigned long long* first_err = (unsigned long long*)(w + 4 * A);
+  void* tmp = w + 4 * A + 256;
+  auto pass = [&](int mode) {
+    hipLaunchKernelGGL(k_rr_seq, dim3((unsigned)R), dim3(64), 0, st, T, mode,
+                       row_count, row_last,
+                       (const uint8_t*)(seek ? sought : nullptr),
+                       (const int64_t*)row_out, capacity, ts_ms, val, is_float,
+                       cnt, first_err);
+  };
+  // counted: an earlier call on the same rows (ts_ms null) left the row
+  // output offsets and the sought marks here: only the write pass runs, and
+  // the caller's pipeline follows it on the same stream (no synchronise)
+  if (counted) {
+    if (R > 0) pass(2);
+    HIP_TRY(hipGetLastError());
+    return OTSDB_OK;
+  }
+  HIP_TRY(hipMemsetAsync(first_err, 0xFF, 8, st));
+  HIP_TRY(hipMemsetAsync(row_count + R, 0, 8, st));
+  if (R > 0) {
+    pass(0);
+    if (seek) {
+      HIP_TRY(hipMemsetAsync(sought, 0, (size_t)R, st));
+      hipLaunchKernelGGL(k_rr_sought, dim3(blocks_for(R, 256)), dim3(256), 0,
+                         st, T, (const int64_t*)row_count,
+                         (const int64_t*)row_last, sought);
+      pass(1);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  if ((rc = scan_excl(tmp, tmpb, row_count, row_out, R, st))) return rc;
+  hipLaunchKernelGGL(k_series_offsets, dim3(blocks_for(R + 1, 256)), dim3(256),
+                     0, st, R, S, raw->row_series, (const int64_t*)row_out,
+                     offsets);
+  HIP_TRY(hipMemcpyAsync(&c->h_small[0], first_err, 8, hipMemcpyDeviceToHost,
+                         st));
+  HIP_TRY(hipMemcpyAsync(&c->h_small[1], row_out + R, 8, hipMemcpyDeviceToHost,
+                         st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const unsigned long long fe = (unsigned long long)c->h_small[0];
+  if (fe != ~0ULL) {
+    const long long row = (long long)(fe >> 8);
+    switch ((int)(fe & 0xFF)) {
+      case RR_ILLEGAL_DATA:
+        return fail(OTSDB_E_ILLEGAL_DATA,
+                    "rollup row %lld: a cell of another aggregator, a value "
+                    "offset going back, or value bytes that do not match the "
+                    "qualifier", row);
+      case RR_ILLEGAL_ARGUMENT:
+        return fail(OTSDB_E_ILLEGAL_ARGUMENT,
+                    "rollup row %lld: a count offset is <= the last offset",
+                    row);
+      default:
+        return fail(OTSDB_E_UNSUPPORTED,
+                    "rollup row %lld: a millisecond qualifier, more than %d "
+                    "columns, or base times that do not increase", row,
+                    kRrRowCols);
+    }
+  }
+  const int64_t total = c->h_small[1];
+  if (!ts_ms) return OTSDB_OK;
+  if (total > capacity)
+    return fail(OTSDB_E_CAPACITY, "decode capacity %lld < %lld points",
+                (long long)capacity, (long long)total);
+  if (R > 0) pass(2);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  return OTSDB_OK;
+}
+
+// The timestamp the query's downsampler hands its source
+// (Downsampler.seekInterval, Downsampler.java:412-434): "all" seeks to the
+// window's start as given, a calendar to the first edge at or after it, a
+// fixed interval to the start rounded up to a multiple of it.
+int64_t rollup_seek_ms(const otsdb_query_spec* s) {
+  if (s->run_all) return s->start_ms;
+  if (s->use_calendar && s->cal_edges && s->n_cal_edges > 0) {
+    const int64_t* e = s->cal_edges;
+    const int64_t* p = std::lower_bound(e, e + s->n_cal_edges, s->start_ms);
+    return p == e + s->n_cal_edges ? s->start_ms : *p;
+  }
+  const int64_t iv = s->ds_interval_ms;
+  return align_down(s->start_ms + iv - 1, iv);
+}
+
+// device pointers throughout: the rows decoded into the context's columnar
+// buffer, then otsdb_agg_run_rollup_device's pipeline over it
+otsdb_status run_rollup_rows_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
+                                  const otsdb_raw_rows* raw,
+                                  const otsdb_rollup_table* t, int32_t agg,
+                                  const otsdb_batch* b, otsdb_result* out,
+                                  std::vector<int64_t>& goff) {
+  hipStream_t st = c->stream;
+  const int64_t S = b->n_series;
+  otsdb_status rc =
+      ensure(&c->cells_ws, &c->cells_ws_cap, (size_t)(S + 1) * 8 + 64);
+  if (rc) return rc;
+  int64_t* offs = (int64_t*)c->cells_ws;
+  const int64_t seek_ms = rollup_seek_ms(spec);
+  // the decode (its own stage; released before the pipeline)
+  std::unique_ptr<StageTimer> dec_tm(new StageTimer(c, 7));
+  rc = rollup_decode_impl(c, raw, t, agg, S, seek_ms, offs, nullptr, nullptr,
+                          nullptr, nullptr, 0, st);
+  if (rc) return rc;
+  const int64_t N = c->h_small[1];
+  const size_t col = ((size_t)std::max<int64_t>(N, 2) * 8 + 255) & ~(size_t)255;
+  rc = ensure(&c->cells_col, &c->cells_col_cap, 4 * col + 256);
+  if (rc) return rc;
+  int64_t* ts = (int64_t*)c->cells_col;
+  int64_t* vv = (int64_t*)((char*)c->cells_col + col);
+  int64_t* cnt = (int64_t*)((char*)c->cells_col + 2 * col);
+  uint8_t* isf = (uint8_t*)((char*)c->cells_col + 3 * col);
+  rc = rollup_decode_impl(c, raw, t, agg, S, seek_ms, offs, ts, vv, isf, cnt, N,
+                          st, true);
+  dec_tm.reset();
+  if (rc) return rc;
+  otsdb_batch cb = *b;
+  cb.n_points = N;
+  cb.offsets = offs;
+  cb.ts_ms = ts;
+  cb.val = vv;
+  cb.is_float = isf;
+  cb.series_float = nullptr;
+  return run_rollup_impl(c, spec, &cb, Rollup{agg, cnt}, out, goff);
 }
 
 // ----------------------------------- multi-aggregator and panel queries
@@ -5309,14 +5509,17 @@ otsdb_status otsdb_agg_run_raw_device(otsdb_ctx* c, const otsdb_query_spec* spec
   return rc;
 }
 
-otsdb_status otsdb_agg_run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
-                               const otsdb_raw_rows* raw, int32_t fix_duplicates,
-                               const otsdb_batch* b, otsdb_result* out) {
-  if (!c || !spec || !raw || !b || !out)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+// The host-pointer entries over storage rows: the rows, the groups and the
+// result staged in HBM; check: the entry's argument checks; run: its device
+// implementation over the staged copies.
+}  // extern "C" (a template has C++ linkage)
+template <class Check, class Run>
+static otsdb_status run_rows_host(otsdb_ctx* c, const otsdb_raw_rows* raw,
+                                  const otsdb_batch* b, otsdb_result* out,
+                                  Check check, Run run) {
   CtxLock lk(c);
   HIP_TRY(hipSetDevice(c->device));
-  otsdb_status rc = check_spec(spec);
+  otsdb_status rc = check();
   if (rc) return rc;
   std::vector<int64_t> goff;
   if ((rc = read_goff(c, b, false, goff))) return rc;
@@ -5400,7 +5603,7 @@ otsdb_status otsdb_agg_run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
   dres.val = (int64_t*)pp[12];
   dres.is_int = (uint8_t*)pp[13];
   c->result_short = false;
-  rc = run_raw_impl(c, spec, &dr, fix_duplicates != 0, &db, &dres, goff);
+  rc = run(&dr, &db, &dres, goff);
   if (rc == OTSDB_E_CAPACITY && c->result_short)
     return copy_offsets_back(c, out, dres.offsets, G, rc);
   if (rc) return rc;
@@ -5415,6 +5618,90 @@ otsdb_status otsdb_agg_run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
   }
   HIP_TRY(hipStreamSynchronize(st));
   return OTSDB_OK;
+}
+extern "C" {
+
+otsdb_status otsdb_agg_run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
+                               const otsdb_raw_rows* raw, int32_t fix_duplicates,
+                               const otsdb_batch* b, otsdb_result* out) {
+  if (!c || !spec || !raw || !b || !out)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  return run_rows_host(
+      c, raw, b, out, [&] { return check_spec(spec); },
+      [&](const otsdb_raw_rows* dr, const otsdb_batch* db, otsdb_result* dres,
+          std::vector<int64_t>& goff) {
+        return run_raw_impl(c, spec, dr, fix_duplicates != 0, db, dres, goff);
+      });
+}
+
+otsdb_status otsdb_rollup_decode_rows_device(
+    otsdb_ctx* c, const otsdb_raw_rows* raw, const otsdb_rollup_table* table,
+    int32_t rollup_agg_id, int64_t n_series, int64_t seek_ms, int64_t* offsets,
+    int64_t* ts_ms, int64_t* val, uint8_t* is_float, int64_t* value_count,
+    int64_t capacity, void* hip_stream) {
+  // (the argument checks first: they need no context)
+  otsdb_status rc = check_rollup_table(raw, table, rollup_agg_id);
+  if (rc) return rc;
+  if (!c || !offsets) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  if (ts_ms && (!val || !is_float ||
+                (rollup_agg_id == OTSDB_AGG_AVG && !value_count)))
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null output column");
+  CtxLock lk(c);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  return rollup_decode_impl(c, raw, table, rollup_agg_id, n_series, seek_ms,
+                            offsets, ts_ms, val, is_float, value_count,
+                            capacity, st);
+}
+
+// check_rollup's refusals with the counts still to come (the decode writes
+// them), then the table's
+static otsdb_status check_rollup_rows(const otsdb_query_spec* spec,
+                                      const otsdb_raw_rows* raw,
+                                      const otsdb_rollup_table* table,
+                                      int32_t agg) {
+  static const int64_t kPending = 0;
+  RollupKind kind;
+  const otsdb_status rc = check_rollup(spec, Rollup{agg, &kPending}, &kind);
+  return rc ? rc : check_rollup_table(raw, table, agg);
+}
+
+otsdb_status otsdb_agg_run_rollup_rows_device(
+    otsdb_ctx* c, const otsdb_query_spec* spec, const otsdb_raw_rows* raw,
+    const otsdb_rollup_table* table, int32_t rollup_agg_id,
+    const otsdb_batch* b, otsdb_result* out, void* hip_stream) {
+  if (!spec || !raw || !table || !b || !out)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  // (the argument checks first: they need no context)
+  const otsdb_status rc = check_rollup_rows(spec, raw, table, rollup_agg_id);
+  if (rc) return rc;
+  if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null context");
+  DeviceCall dc(c, b, hip_stream);
+  return dc.rc ? dc.rc
+               : run_rollup_rows_impl(c, spec, raw, table, rollup_agg_id, b,
+                                      out, dc.goff);
+}
+
+otsdb_status otsdb_agg_run_rollup_rows(otsdb_ctx* c,
+                                       const otsdb_query_spec* spec,
+                                       const otsdb_raw_rows* raw,
+                                       const otsdb_rollup_table* table,
+                                       int32_t rollup_agg_id,
+                                       const otsdb_batch* b,
+                                       otsdb_result* out) {
+  if (!spec || !raw || !table || !b || !out)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  // (the argument checks first: they need no context)
+  const otsdb_status rc = check_rollup_rows(spec, raw, table, rollup_agg_id);
+  if (rc) return rc;
+  if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null context");
+  return run_rows_host(
+      c, raw, b, out, [] { return OTSDB_OK; },
+      [&](const otsdb_raw_rows* dr, const otsdb_batch* db, otsdb_result* dres,
+          std::vector<int64_t>& goff) {
+        return run_rollup_rows_impl(c, spec, dr, table, rollup_agg_id, db,
+                                    dres, goff);
+      });
 }
 
 otsdb_status otsdb_agg_run_cells(otsdb_ctx* c, const otsdb_query_spec* spec,

@@ -184,6 +184,33 @@ def rollup_args(spec, rollup_agg, value_count):
     return r, value_count
 
 
+def rollup_rows_args(spec, rollup_agg, table):
+    """The rollup arguments of a call over a rollup table's storage rows:
+    (rollup aggregator id, abi.RollupTable).  rollup_args' checks with the
+    counts still to come (the decode pairs them), then the table's.  `table`:
+    an abi.RollupTable or (interval_s, value_id, count_id, fix_duplicates)."""
+    r, _ = rollup_args(spec, rollup_agg, True)
+    if not isinstance(table, abi.RollupTable):
+        table = abi.RollupTable(*[int(v) for v in table])
+    if table.interval_s <= 0:
+        raise IllegalArgumentException(
+            "rollup interval %d s" % table.interval_s)
+    return r, table
+
+
+def _groups_abi(batch):
+    """The otsdb_batch of a call whose points come from storage rows:
+    n_series and the groups of `batch` (host arrays), no point arrays."""
+    b = abi.Batch()
+    b.n_series = batch.n_series
+    b.n_points = 0
+    b.n_groups = batch.n_groups
+    b.group_offsets = batch.group_offsets.ctypes.data
+    b.group_members = (batch.group_members.ctypes.data
+                       if len(batch.group_members) else None)
+    return b
+
+
 def _host_results(n, G, cap):
     """n host results of capacity `cap` for G groups: the abi.Result array
     and a function that slices them into one list of DataPoints (one per
@@ -318,6 +345,26 @@ class Engine:
         self._check(self.lib.otsdb_agg_run_rollup(
             self.ctx, C.byref(spec), C.byref(b), r,
             None if vc is None else vc.ctypes.data, rs))
+        return points()[0]
+
+    def run_rollup_rows(self, spec, rows, table, rollup_agg, batch):
+        """run_rollup() from a rollup table's storage rows (host arrays):
+        `rows` is a storage.HostRawRows of the scanner's rows (one column per
+        cell), `table` an abi.RollupTable (or its four fields), `rollup_agg`
+        the table's aggregator; `batch` supplies n_series and the groups (its
+        point arrays are not read).  The sum and count cells are paired and
+        decoded on the device.  Results as run()'s."""
+        r, table = rollup_rows_args(spec, rollup_agg, table)
+        b = _groups_abi(batch)
+        sz = abi.Sizes()
+        self._check(self.lib.otsdb_agg_plan(self.ctx, C.byref(spec),
+                                            C.byref(b), C.byref(sz)))
+        rs, points = _host_results(1, batch.n_groups,
+                                   max(1, int(sz.max_out_points)))
+        raw = rows.as_abi()
+        self._check(self.lib.otsdb_agg_run_rollup_rows(
+            self.ctx, C.byref(spec), C.byref(raw), C.byref(table), r,
+            C.byref(b), rs))
         return points()[0]
 
     def plan_multi(self, spec, aggs, batch, interps=None):
@@ -520,6 +567,60 @@ def run_rollup_device(engine, spec, dbatch, rollup_agg, dcount, dresult,
     engine._check(engine.lib.otsdb_agg_run_rollup_device(
         engine.ctx, C.byref(spec), C.byref(b), r,
         None if vc is None else vc.data_ptr(), C.byref(res), _stream(stream)))
+
+
+def run_rollup_rows_device(engine, spec, draw, table, rollup_agg, dbatch,
+                           dresult, stream=None):
+    """Device-resident Engine.run_rollup_rows: `draw` is a
+    storage.DeviceRawRows, `dbatch` supplies n_series and the groups."""
+    r, table = rollup_rows_args(spec, rollup_agg, table)
+    b = abi.Batch()
+    b.n_series = dbatch.n_series
+    b.n_points = 0
+    b.n_groups = dbatch.n_groups
+    b.group_offsets = dbatch.group_offsets.data_ptr()
+    b.group_members = dbatch.group_members.data_ptr()
+    raw = draw.as_abi()
+    res = dresult.as_abi()
+    engine._check(engine.lib.otsdb_agg_run_rollup_rows_device(
+        engine.ctx, C.byref(spec), C.byref(raw), C.byref(table), r,
+        C.byref(b), C.byref(res), _stream(stream)))
+
+
+def rollup_decode_rows_device(engine, draw, table, rollup_agg, n_series,
+                              seek_ms=None, stream=None):
+    """otsdb_rollup_decode_rows_device: the rows of a rollup table (a
+    storage.DeviceRawRows) paired and decoded into torch tensors (offsets
+    [n_series + 1], ts_ms, val, is_float, value_count) on the rows' device;
+    value_count is None unless the rollup aggregator is avg.  seek_ms: the
+    timestamp the query's downsampler hands its source, None for no seek."""
+    import torch
+    _, ids, _ = multi_args([rollup_agg])
+    r = int(ids[0])
+    if not isinstance(table, abi.RollupTable):
+        table = abi.RollupTable(*[int(v) for v in table])
+    seek = -2 ** 63 if seek_ms is None else int(seek_ms)
+    dev = draw.t["qual"].device
+    offsets = torch.zeros(n_series + 1, dtype=torch.int64, device=dev)
+    raw = draw.as_abi()
+
+    def call(ts, val, isf, cnt, cap):
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        engine._check(engine.lib.otsdb_rollup_decode_rows_device(
+            engine.ctx, C.byref(raw), C.byref(table), r, n_series, seek,
+            offsets.data_ptr(), p(ts), p(val), p(isf), p(cnt), cap,
+            _stream(stream)))
+    call(None, None, None, None, 0)
+    n = int(offsets[-1].item())
+    cap = max(n, 2)  # (never an empty allocation: the pointers must be real)
+    ts = torch.zeros(cap, dtype=torch.int64, device=dev)
+    val = torch.zeros(cap, dtype=torch.int64, device=dev)
+    isf = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    cnt = (torch.zeros(cap, dtype=torch.int64, device=dev)
+           if r == Aggregators.AVG.id else None)
+    call(ts, val, isf, cnt, n)
+    return (offsets, ts[:n], val[:n], isf[:n],
+            None if cnt is None else cnt[:n])
 
 
 def _fold_spec(spec, fold, bit=None):

@@ -1,0 +1,82 @@
+"""The compiler's gfx950 resource report of every kernel of engine.hip
+(hipcc -Rpass-analysis=kernel-resource-usage, build.py's flags), for this tree
+and, with --before, for another checkout of the project (the parent commit):
+which kernels exist on both sides, whether their figures are identical, and
+the figures of the kernels whose names match --new.
+
+    python -m scripts.resource_report --before PATH/TO/PARENT/CHECKOUT \
+        --new k_rr_ --out profiles/rollup_rows_resources.json
+"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+FIELDS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]",
+          "Dynamic Stack", "Occupancy [waves/SIMD]", "SGPRs Spill",
+          "VGPRs Spill", "LDS Size [bytes/block]")
+
+
+def report(root, unit="engine.hip"):
+    """{demangled kernel name: {field: value}} of one translation unit."""
+    from opentsdb_amd import build
+    src = os.path.join(root, "opentsdb_amd", "csrc", unit)
+    cmd = [build.HIPCC] + build.FLAGS + [
+        "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c",
+        "-o", os.devnull, src]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True, check=True)
+    out, cur = {}, None
+    for line in r.stdout.splitlines():
+        m = re.search(r"remark: .*Function Name: (\S+)", line)
+        if m:
+            cur = out.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark: +([A-Za-z][^:]*): (\S+) \[-Rpass", line)
+        if m and cur is not None and m.group(1).strip() in FIELDS:
+            cur[m.group(1).strip()] = m.group(2).strip()
+    names = sorted(out)
+    dem = subprocess.run(["c++filt"] + names,
+                         stdout=subprocess.PIPE, text=True).stdout.split("\n")
+    return {d or n: out[n] for n, d in zip(names, dem)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--before", default=None, help="the parent's checkout")
+    ap.add_argument("--new", default="k_rr_",
+                    help="substring of the new kernels' names")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    after = report(ROOT)
+    doc = {"arch": "gfx950",
+           "source": "hipcc " + " ".join(__import__(
+               "opentsdb_amd.build", fromlist=["FLAGS"]).FLAGS[1:5]) +
+           " -Rpass-analysis=kernel-resource-usage: engine.hip (the one unit "
+           "that includes rollup_rows.hip; the ds_tu.hip and rollup.hip units "
+           "do not, and are built from unchanged sources with unchanged "
+           "flags); before = the parent commit",
+           "new": {k: v for k, v in after.items() if a.new in k}}
+    if a.before:
+        before = report(a.before)
+        old = {k: v for k, v in after.items() if a.new not in k}
+        doc["engine.hip"] = {
+            "kernels_before": len(before), "kernels_after": len(old),
+            "kernels_only_before": sorted(set(before) - set(old)),
+            "kernels_only_after": sorted(set(old) - set(before)),
+            "kernels_with_other_figures": sorted(
+                k for k in before if k in old and before[k] != old[k])}
+    print(json.dumps(doc, indent=1))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(doc, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
