@@ -94,7 +94,7 @@ def build(force=False, verbose=False, jobs=None, defines=(), out=None):
     # kernels.hip, decode.hip, fold.hip, cellfold.hip and the headers)
     engine_only = ("engine.hip", "select.hip", "raw.hip", "rows.hip",
                    "rollup_rows.hip", "calendar.hip", "compact.hip",
-                   "multi.hip", "panel.hip")
+                   "multi.hip", "panel.hip", "foldplan.h")
 
     def stale(u):
         src, extra, obj = u

@@ -45,6 +45,9 @@
 #ifndef OTSDB_RATE_PF
 #define OTSDB_RATE_PF 0
 #endif
+#include <string>
+#include <type_traits>
+
 #include "kernels.hip"
 #include "decode.hip"
 #include "fold.hip"
@@ -62,34 +65,60 @@ inline unsigned ds_blocks(int64_t n, int per) {
 }  // namespace
 
 #if OTSDB_DS_PART == 1
-// the cells fold: prep + k_fold<M, A, 8, 1> x every aggregator, and
+// the cells fold: prep + k_fold<M, A, 8, CELLS> x every aggregator, and
 // k_fold_multi's cells variants over the envelope state
+
+// DsLaunch.cells_variant as the kernels' compile-time CELLS; walker: the
+// debug name of its qualifier width and member walker
+template <class F>
+bool with_cells_variant(int variant, F&& f) {
+  switch (variant) {
+    case 2: return f(std::integral_constant<int, 2>{}, "cells, qw 2");
+    case 4: return f(std::integral_constant<int, 4>{}, "cells, qw 4");
+    case 10: return f(std::integral_constant<int, 10>{}, "cells, qw 2, uniform");
+    case 12: return f(std::integral_constant<int, 12>{}, "cells, qw 4, uniform");
+    default: return false;
+  }
+}
+
 template <class M, int CELLS>
-void launch_cells_multi(const DsLaunch& a, const char* what) {
+bool launch_cells_fold(const DsLaunch& a, const char* walker) {
+  return with_monoid(a.agg_id, [&](auto tag) {
+    using A = decltype(tag);
+    hipLaunchKernelGGL((k_fold<M, A, 8, CELLS>),
+                       dim3((unsigned)(a.n_tiles * a.NW)), dim3(FOLD_THREADS),
+                       (unsigned)fold_lds_bytes<A>(a.P),
+                       a.st, a.P, a.B, a.SM, a.n_tiles, a.tg, a.tm0,
+                       a.tm1, a.single, a.members, a.wc, a.NW, a.partial,
+                       a.tile_emit, a.out_val, a.out_emit, a.err,
+                       a.always_partial, a.cf);
+    OTSDB_DBG(a.st, (std::string("k_fold<") + walker + ">").c_str());
+  });
+}
+
+template <class M, int CELLS>
+bool launch_cells_multi(const DsLaunch& a, const char* walker) {
   hipLaunchKernelGGL((k_fold_multi<M, 8, CELLS>),
                      dim3((unsigned)(a.n_tiles * a.NW)), dim3(FOLD_THREADS),
                      (unsigned)fold_lds_bytes<MEnv>(a.P), a.st, a.P, a.B, a.SM,
                      a.n_tiles, a.tg, a.tm0, a.tm1, a.single, a.members, a.wc,
                      a.NW, a.tile_emit, a.err, *a.fm, a.cf);
-  OTSDB_DBG(a.st, what);
+  OTSDB_DBG(a.st, (std::string("k_fold_multi<") + walker + ">").c_str());
+  return true;
 }
 
 template <class M>
 bool launch_cells(DsKernel k, const DsLaunch& a) {
   const int64_t S = a.B.S;
   switch (k) {
-    case DS_CELLS_MULTI2:
-      launch_cells_multi<M, 2>(a, "k_fold_multi<cells, qw 2>");
-      return true;
-    case DS_CELLS_MULTI4:
-      launch_cells_multi<M, 4>(a, "k_fold_multi<cells, qw 4>");
-      return true;
-    case DS_CELLS_MULTI2U:
-      launch_cells_multi<M, 10>(a, "k_fold_multi<cells, qw 2, uniform>");
-      return true;
-    case DS_CELLS_MULTI4U:
-      launch_cells_multi<M, 12>(a, "k_fold_multi<cells, qw 4, uniform>");
-      return true;
+    case DS_CELLS_FOLD:
+      return with_cells_variant(a.cells_variant, [&](auto v, const char* w) {
+        return launch_cells_fold<M, decltype(v)::value>(a, w);
+      });
+    case DS_CELLS_MULTI:
+      return with_cells_variant(a.cells_variant, [&](auto v, const char* w) {
+        return launch_cells_multi<M, decltype(v)::value>(a, w);
+      });
     case DS_CELLS_PREP:
       if (S > 0)
         hipLaunchKernelGGL(k_cells_prep<M>, dim3(ds_blocks(S, OTSDB_PREP_TPB)),
@@ -105,60 +134,12 @@ bool launch_cells(DsKernel k, const DsLaunch& a) {
                            a.st, a.P, a.cf, S, a.SM, a.NW, a.WB, a.wc, a.err);
       OTSDB_DBG(a.st, "k_cells_fold_prep");
       return true;
-    case DS_CELLS_FOLD4:
-      return with_monoid(a.agg_id, [&](auto tag) {
-        using A = decltype(tag);
-        hipLaunchKernelGGL((k_fold<M, A, 8, 4>),
-                           dim3((unsigned)(a.n_tiles * a.NW)), dim3(FOLD_THREADS),
-                           (unsigned)fold_lds_bytes<A>(a.P),
-                           a.st, a.P, a.B, a.SM, a.n_tiles, a.tg, a.tm0,
-                           a.tm1, a.single, a.members, a.wc, a.NW, a.partial,
-                           a.tile_emit, a.out_val, a.out_emit, a.err,
-                           a.always_partial, a.cf);
-        OTSDB_DBG(a.st, "k_fold<cells, qw 4>");
-      });
     case DS_CELLS_UNIFORM:
       if (S > 0)
         hipLaunchKernelGGL(k_cells_uniform<M>, dim3(ds_blocks(S, 4)), dim3(256),
                            0, a.st, a.cf, S, a.SM);
       OTSDB_DBG(a.st, "k_cells_uniform");
       return true;
-    case DS_CELLS_FOLD4U:
-      return with_monoid(a.agg_id, [&](auto tag) {
-        using A = decltype(tag);
-        hipLaunchKernelGGL((k_fold<M, A, 8, 12>),
-                           dim3((unsigned)(a.n_tiles * a.NW)), dim3(FOLD_THREADS),
-                           (unsigned)fold_lds_bytes<A>(a.P),
-                           a.st, a.P, a.B, a.SM, a.n_tiles, a.tg, a.tm0,
-                           a.tm1, a.single, a.members, a.wc, a.NW, a.partial,
-                           a.tile_emit, a.out_val, a.out_emit, a.err,
-                           a.always_partial, a.cf);
-        OTSDB_DBG(a.st, "k_fold<cells, qw 4, uniform>");
-      });
-    case DS_CELLS_FOLD2U:
-      return with_monoid(a.agg_id, [&](auto tag) {
-        using A = decltype(tag);
-        hipLaunchKernelGGL((k_fold<M, A, 8, 10>),
-                           dim3((unsigned)(a.n_tiles * a.NW)), dim3(FOLD_THREADS),
-                           (unsigned)fold_lds_bytes<A>(a.P),
-                           a.st, a.P, a.B, a.SM, a.n_tiles, a.tg, a.tm0,
-                           a.tm1, a.single, a.members, a.wc, a.NW, a.partial,
-                           a.tile_emit, a.out_val, a.out_emit, a.err,
-                           a.always_partial, a.cf);
-        OTSDB_DBG(a.st, "k_fold<cells, qw 2, uniform>");
-      });
-    case DS_CELLS_FOLD2:
-      return with_monoid(a.agg_id, [&](auto tag) {
-        using A = decltype(tag);
-        hipLaunchKernelGGL((k_fold<M, A, 8, 2>),
-                           dim3((unsigned)(a.n_tiles * a.NW)), dim3(FOLD_THREADS),
-                           (unsigned)fold_lds_bytes<A>(a.P),
-                           a.st, a.P, a.B, a.SM, a.n_tiles, a.tg, a.tm0,
-                           a.tm1, a.single, a.members, a.wc, a.NW, a.partial,
-                           a.tile_emit, a.out_val, a.out_emit, a.err,
-                           a.always_partial, a.cf);
-        OTSDB_DBG(a.st, "k_fold<cells, qw 2>");
-      });
     default:
       return false;
   }
@@ -166,6 +147,21 @@ bool launch_cells(DsKernel k, const DsLaunch& a) {
 #define OTSDB_LAUNCH launch_cells
 #else
 #define OTSDB_LAUNCH launch_ds
+// The dynamic LDS of a columnar fold over states A.  Member contexts are
+// preloaded into LDS only while the workgroup stays within 40 KB (4 a CU:
+// C2's 2,017-bucket windows leave room for 10); otherwise P.fold_ctx is
+// dropped
+template <class A>
+size_t fold_ctx_lds(Params& P) {
+  size_t lds = fold_lds_bytes<A>(P);
+  if (P.fold_ctx > 0 &&
+      lds + (size_t)P.fold_ctx * sizeof(FoldMember) <= kFoldDynBudget)
+    lds += (size_t)P.fold_ctx * sizeof(FoldMember);
+  else
+    P.fold_ctx = 0;
+  return lds;
+}
+
 template <class M>
 bool launch_ds(DsKernel k, const DsLaunch& a) {
   const int64_t S = a.B.S;
@@ -213,15 +209,8 @@ bool launch_ds(DsKernel k, const DsLaunch& a) {
     case DS_FOLD:
       return with_monoid(a.agg_id, [&](auto tag) {
         using A = decltype(tag);
-        // member contexts preloaded into LDS only while the workgroup stays
-        // within 40 KB (4 a CU: C2's 2,017-bucket windows leave room for 10)
         Params P = a.P;
-        size_t lds = fold_lds_bytes<A>(P);
-        if (P.fold_ctx > 0 && lds + (size_t)P.fold_ctx * sizeof(FoldMember) <=
-                                  kFoldDynBudget)
-          lds += (size_t)P.fold_ctx * sizeof(FoldMember);
-        else
-          P.fold_ctx = 0;
+        const size_t lds = fold_ctx_lds<A>(P);
         hipLaunchKernelGGL((k_fold<M, A, 8>),
                            dim3((unsigned)(a.n_tiles * a.NW)), dim3(FOLD_THREADS),
                            (unsigned)lds,
@@ -232,15 +221,10 @@ bool launch_ds(DsKernel k, const DsLaunch& a) {
         OTSDB_DBG(a.st, "k_fold");
       });
     case DS_FOLD_MULTI: {
-      // as DS_FOLD: the contexts only while the workgroup stays 4 to a CU
-      // (full-width windows of 1,024 envelope states leave no room)
+      // (full-width windows of 1,024 envelope states leave the contexts no
+      // room)
       Params P = a.P;
-      size_t lds = fold_lds_bytes<MEnv>(P);
-      if (P.fold_ctx > 0 && lds + (size_t)P.fold_ctx * sizeof(FoldMember) <=
-                                kFoldDynBudget)
-        lds += (size_t)P.fold_ctx * sizeof(FoldMember);
-      else
-        P.fold_ctx = 0;
+      const size_t lds = fold_ctx_lds<MEnv>(P);
       hipLaunchKernelGGL((k_fold_multi<M, 8>),
                          dim3((unsigned)(a.n_tiles * a.NW)), dim3(FOLD_THREADS),
                          (unsigned)lds, a.st, P, a.B, a.SM, a.n_tiles, a.tg,

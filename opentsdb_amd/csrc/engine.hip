@@ -35,6 +35,7 @@
 #include "multi.hip"
 #include "panel.hip"
 #include "launch.h"
+#include "foldplan.h"
 
 using namespace otsdb;
 
@@ -107,53 +108,19 @@ dim3 kt_grid(int64_t M, int64_t NB) {
   return dim3((unsigned)((M + KT_M - 1) / KT_M), (unsigned)sl);
 }
 
-// members per tile of the ordered fold: one tile is one workgroup that
-// streams all its members' points, so big groups (C3's 7.8k-series
-// datacenters per GPU) are cut finer than kChunk — 256-member tiles of one
-// day of points leave the last round of workgroups half empty (C3 fold:
-// 256 -> 2.9 ms, 64 -> 2.57 ms, 32 -> 2.53 ms)
-#ifndef OTSDB_FOLD_CHUNK  // tuning builds override
-#define OTSDB_FOLD_CHUNK 32
-#endif
-constexpr int64_t kFoldChunk = OTSDB_FOLD_CHUNK;
-// groups of more than kFoldChunk members (C3's 7.8k-series datacenters):
-// tiles of kFoldChunkLarge, twice as many workgroups again for the grid's
-// last round (C3 fold: 32 -> 2.59 ms, 16 -> 2.50, 8 -> 2.46); groups up to
-// kFoldChunk members (C1 / C2 hosts) stay one tile
-#ifndef OTSDB_FOLD_CHUNK_LARGE  // tuning builds override
-#define OTSDB_FOLD_CHUNK_LARGE 8
-#endif
-constexpr int64_t kFoldChunkLarge = OTSDB_FOLD_CHUNK_LARGE;
-#ifndef OTSDB_FOLD_CTX  // tuning builds: 0 = no preloaded member contexts
-#define OTSDB_FOLD_CTX 1
-#endif
-// Order-sensitive aggregators whose merge of partial states is
-// ill-conditioned (dev: Chan's merge of Welford runs over offset data lands
-// ~1e-11 from the reference's one sequential pass, Aggregators.java:547-568)
-// reduce a group's members in ONE sequential chain per (group, bucket) while
-// the group fits: fold tiles of up to kOrderedFoldChunk members (the LDS
-// progress marks of one workgroup), then the row path's k_group with one
-// chain of up to kOrderedChunk members (one thread walks them in SpanCmp
-// order; ~100 ns a member: tools/chain_probe.hip, 69 ns with no memory at
-// all, so a 500k-member chain — C4 — would cost ~50 ms).  Larger groups
-// merge 256-member chunk partials in order (Chan); across ranks the chain is
-// handed on (otsdb_agg_partials_chained_device).
-constexpr int64_t kOrderedFoldChunk = 256;
+// (the ordered fold's tile sizes and window rule: foldplan.h)
+// An ordered (dev) group past one fold tile (kOrderedFoldChunk) takes the row
+// path's k_group with one chain of up to kOrderedChunk members (one thread
+// walks them in SpanCmp order; ~100 ns a member: tools/chain_probe.hip, 69 ns
+// with no memory at all, so a 500k-member chain — C4 — would cost ~50 ms).
+// Larger groups merge 256-member chunk partials in order (Chan); across ranks
+// the chain is handed on (otsdb_agg_partials_chained_device).
 constexpr int64_t kOrderedChunk = 65536;
 constexpr int64_t kOrderedChunkMerged = 16384;
 // the row path's bucket rows an ordered (dev) query may take for groups past
 // one fold tile: fixed, so the path (and the reduction order) never depends
 // on the device's free memory at call time
 constexpr double kOrderedRowBudget = 48.0e9;
-// below this many (tile, window) workgroups the fold narrows its windows,
-// down to kFoldMinWindow buckets
-#ifndef OTSDB_FOLD_MIN_BLOCKS  // tuning builds override
-#define OTSDB_FOLD_MIN_BLOCKS 1024
-#endif
-#ifndef OTSDB_FOLD_MIN_WINDOW
-#define OTSDB_FOLD_MIN_WINDOW 128
-#endif
-constexpr int64_t kFoldMinBlocks = OTSDB_FOLD_MIN_BLOCKS;
 // up to this many (series, window boundary) pairs k_prep and k_fold_prep run
 // as one launch (each pair's thread finds its series' bounds again: cheap
 // next to a launch on small queries, not on the named query's 400,000)
@@ -166,7 +133,6 @@ int64_t prep_fold_max() {
   const char* e = getenv("OTSDB_PREP_FOLD_MAX");
   return e ? atoll(e) : (int64_t)OTSDB_PREP_FOLD_MAX;
 }
-constexpr int64_t kFoldMinWindow = OTSDB_FOLD_MIN_WINDOW;
 
 // the storage rows cannot be taken verbatim (run_raw_verbatim): flagged on
 // the context, never returned through the C-ABI
@@ -946,6 +912,88 @@ bool fold_path(const otsdb_query_spec* spec, const Params& P, int mode) {
          mode != 2;
 }
 
+// ---- the fold's launch, shared by run_pipeline and multi_fold_pass --------
+// The cells fold's per-series cursors (launch.h CellsFold), carved where the
+// caller's layout has them; NW: the windows of THIS fold's state.
+void carve_cells_fold(Carve& cv, CellsFold& CF, otsdb_ctx* c,
+                      const CellsDev& cells, const int64_t* series_row,
+                      int64_t S, int64_t NW) {
+  CF.C = cells;
+  CF.series_row = series_row;
+  CF.wide = c->d_err + 1;
+  CF.rlo = cv.take<int64_t>(S);
+  CF.vlo = cv.take<int64_t>(S);
+  CF.qw = cv.take<uint8_t>(S);
+  CF.vl0 = cv.take<uint8_t>(S);
+  CF.uf = cv.take<uint8_t>(S);
+  if (NW > 1) {
+    CF.wrlo = cv.take<int64_t>((size_t)S * (NW - 1));
+    CF.wvlo = cv.take<int64_t>((size_t)S * (NW - 1));
+    CF.wvl0 = cv.take<uint8_t>((size_t)S * (NW - 1));
+  }
+}
+
+// the tiles and windows of a fold, for its prep kernels and the fold itself
+void fold_args(DsLaunch& a, const Tiles& T, const int64_t* d_members,
+               WinCtx* wc, int64_t NW, int64_t WB, uint8_t* tile_emit) {
+  a.n_tiles = T.T;
+  a.tg = T.tg;
+  a.tm0 = T.tm0;
+  a.tm1 = T.tm1;
+  a.single = T.single;
+  a.members = d_members;
+  a.wc = wc;
+  a.NW = NW;
+  a.WB = WB;
+  a.tile_emit = tile_emit;
+}
+
+// every series' bounds and, for grids of several windows, its context at
+// each inner window boundary; cells: from compacted columns (a.cf)
+template <class M>
+void fold_prep(otsdb_ctx* c, const DsLaunch& a, bool cells) {
+  StageTimer tm(c, 3);
+  if (cells) {
+    launch_cells<M>(DS_CELLS_PREP, a);
+    if (!c->cells_no_uni) launch_cells<M>(DS_CELLS_UNIFORM, a);
+    if (a.NW > 1) launch_cells<M>(DS_CELLS_FOLD_PREP, a);
+  } else if (a.NW > 1 && a.B.S * (a.NW - 1) <= prep_fold_max()) {
+    launch_ds<M>(DS_PREP_FOLD, a);
+  } else {
+    launch_ds<M>(DS_PREP, a);
+    if (a.NW > 1) launch_ds<M>(DS_FOLD_PREP, a);
+  }
+}
+
+// Which cells fold kernel runs (DsLaunch.cells_variant), 0: none.  The
+// kernels fix the qualifier width at compile time (one copy of the member
+// loop per kernel: 14 % faster on C2's cells than a width read per member).
+// k_cells_prep's bits 0 / 1: 4- / 2-byte series kept; both ->
+// ERR_CELLS_GENERIC and nothing is launched: the engine rewrites the batch
+// with one width (k_requal) and runs again.  k_cells_uniform's bit 2: some
+// kept series is not uniform (or the uniform kernel already missed in this
+// call): the general walker.  Waits for the prep kernels.
+int cells_fold_variant(otsdb_ctx* c) {
+  hipStream_t st = c->stream;
+  int widths = 3;
+  bool uniform = false;
+  if (hipMemcpyAsync(&c->h_small[2], c->d_err, 2 * sizeof(int),
+                     hipMemcpyDeviceToHost, st) == hipSuccess &&
+      hipStreamSynchronize(st) == hipSuccess) {
+    widths = (int)((c->h_small[2] >> 32) & 3);
+    uniform = !c->cells_no_uni && !((c->h_small[2] >> 32) & 4);
+  }
+  if (widths == 3) {
+    const int e = (int)(c->h_small[2] & 0xFFFFFFFF) | ERR_CELLS_GENERIC;
+    c->h_small[3] = e;
+    hipMemcpyAsync(c->d_err, &c->h_small[3], sizeof(int),
+                   hipMemcpyHostToDevice, st);
+    return 0;
+  }
+  ++(uniform ? c->n_cells_uniform : c->n_cells_general);
+  return (widths == 1 ? 4 : 2) + (uniform ? 8 : 0);
+}
+
 // ---- the row path, part 1: "build the rows" ------------------------------
 // Per-series bucket rows W.R from the point stream (or the compacted
 // columns): prep + k_bucketize_k / the rate-fused ring / k_ds_select /
@@ -1151,6 +1199,96 @@ otsdb_status group_rows(otsdb_ctx* c, int agg_id, const Work& W,
   return OTSDB_OK;
 }
 
+// Which path a query takes and how its groups are tiled.  Values only: no
+// device state is touched.
+struct Route {
+  bool fold;       // the ordered group fold (else the row path)
+  bool ordered;    // the aggregator reduces a group in one chain (dev)
+  int64_t wb_cap;  // fold: the most buckets of a window, fold_wb<A>()
+  int64_t chunk, whole_upto;  // build_tiles' cut of the groups
+};
+
+// cells: the series come as compacted columns; chained: the chains continue
+// a previous rank's states (ginit)
+otsdb_status route_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
+                            const std::vector<int64_t>& goff, const Params& P,
+                            int64_t S, int mode, bool cells, bool chained,
+                            Route* R) {
+  const int64_t NB = P.nb;
+  // chained partials continue each group's state in k_group (the row path)
+  // (a rollup call's states exist only for the row path's prep and ring)
+  bool fold = fold_path(spec, P, mode) && !chained && !c->rollup;
+  int64_t WB = 0;
+  if (fold && !with_monoid(spec->agg_id, [&](auto tag) {
+        WB = fold_wb<decltype(tag)>();
+      }))
+    return fail(OTSDB_E_NO_SUCH_ELEMENT, "aggregator %d", spec->agg_id);
+  // the cells fold runs on narrow grids (32-bit times), windows after the
+  // first starting from k_cells_fold_prep's cursors; calendar grids from
+  // cells take k_bucketize_cells and the row pipeline
+  if (cells && !P.narrow) fold = false;
+  bool ordered = false;
+  with_monoid(spec->agg_id, [&](auto tag) {
+    ordered = decltype(tag)::kOrdered;
+  });
+  // OTSDB_SPEC_EXACT_ORDER: every group one chain, whatever its size
+  const bool exact = ordered && (spec->flags & OTSDB_SPEC_EXACT_ORDER) != 0;
+  if (ordered && fold) {
+    // a group past one fold tile takes the row path (one chain per bucket)
+    // when its bucket matrix (8-byte value + state byte per series and
+    // bucket) fits the fixed row budget — a bound of the query alone, so
+    // identical queries always take the same path (and the same order);
+    // otherwise the fold's tiles stay, merged in order (Chan) like a group
+    // past the exact-chain bound, or E_CAPACITY when the caller asked for
+    // the exact order
+    int64_t kmax = 0;
+    for (size_t g = 0; g + 1 < goff.size(); ++g)
+      kmax = std::max(kmax, goff[g + 1] - goff[g]);
+    if (kmax > kOrderedFoldChunk) {
+      if ((double)S * (double)NB * 9.0 <= kOrderedRowBudget) {
+        fold = false;
+      } else if (exact) {
+        return fail(OTSDB_E_CAPACITY,
+                    "exact-order dev: %lld x %lld bucket rows past the row "
+                    "budget", (long long)S, (long long)NB);
+      }
+    }
+  }
+  const bool cfold = cells && fold;
+  // verbatim storage rows: the single-window cells fold only (it checks
+  // what compaction would change; window boundaries it does not see)
+  if (c->verbatim && (!cfold || NB > WB)) return spec_miss(c);
+  // the chained entry always takes the row path (its chains continue from
+  // the previous rank's states): past the row budget a clear E_CAPACITY
+  if (chained && (double)S * (double)NB * 9.0 > kOrderedRowBudget)
+    return fail(OTSDB_E_CAPACITY,
+                "chained partials: %lld x %lld bucket rows past the row budget",
+                (long long)S, (long long)NB);
+  if (exact && mode == 1 && !chained)
+    return fail(OTSDB_E_UNSUPPORTED,
+                "exact-order dev across ranks: hand the chains on "
+                "(otsdb_agg_partials_chained_device)");
+  R->fold = fold;
+  R->ordered = ordered;
+  R->wb_cap = WB;
+  if (fold) {
+    const FoldTiling ft = fold_tiling(ordered);
+    R->chunk = ft.chunk;
+    R->whole_upto = ft.whole_upto;
+  } else {
+    // the row path's k_group: one chain per (group, bucket) up to
+    // kOrderedChunk members; partials for the merge across ranks (a group
+    // too large to hand on, dist.py) keep round 4's shorter chains, merged
+    // in order anyway
+    R->chunk = kChunk;
+    R->whole_upto = !ordered ? 0
+                    : exact  ? INT64_MAX
+                    : mode == 1 && !chained ? kOrderedChunkMerged
+                                            : kOrderedChunk;
+  }
+  return OTSDB_OK;
+}
+
 // Everything up to dense (group, bucket) results / partials.
 // mode 0: final dense results; mode 1: per-group partials into `gpart/gemit`;
 // mode 2: the cross-rank selection protocol's local part.
@@ -1168,9 +1306,6 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
   const int64_t S = B.S;
   const int64_t G = (int64_t)goff.size() - 1;
   const int64_t nb = P.nb;
-  // chained partials continue each group's state in k_group (the row path)
-  // (a rollup call's states exist only for the row path's prep and ring)
-  bool fold = fold_path(spec, P, mode) && !ginit && !c->rollup;
 
   // grid trimming for very wide windows (NONE fill only): the rows span only
   // the buckets that hold data
@@ -1198,106 +1333,27 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
   if (NB > (int64_t)INT32_MAX - 2)
     return fail(OTSDB_E_UNSUPPORTED, "bucket grid of %lld buckets per series",
                 (long long)NB);
-  int64_t WB = 0, NW = 0;
-  if (fold) {
-    if (!with_monoid(spec->agg_id, [&](auto tag) {
-          WB = fold_wb<decltype(tag)>();
-        }))
-      return fail(OTSDB_E_NO_SUCH_ELEMENT, "aggregator %d", spec->agg_id);
-    NW = (NB + WB - 1) / WB;
-  }
-  // the cells fold runs on narrow grids (32-bit times), windows after the
-  // first starting from k_cells_fold_prep's cursors; calendar grids from
-  // cells take k_bucketize_cells and the row pipeline
-  if (cells && !P.narrow) {
-    fold = false;
-    WB = NW = 0;
-  }
-  bool ordered = false;
-  with_monoid(spec->agg_id, [&](auto tag) {
-    ordered = decltype(tag)::kOrdered;
-  });
-  // OTSDB_SPEC_EXACT_ORDER: every group one chain, whatever its size
-  const bool exact = ordered && (spec->flags & OTSDB_SPEC_EXACT_ORDER) != 0;
-  if (ordered && fold) {
-    // a group past one fold tile takes the row path (one chain per bucket)
-    // when its bucket matrix (8-byte value + state byte per series and
-    // bucket) fits the fixed row budget — a bound of the query alone, so
-    // identical queries always take the same path (and the same order);
-    // otherwise the fold's tiles stay, merged in order (Chan) like a group
-    // past the exact-chain bound, or E_CAPACITY when the caller asked for
-    // the exact order
-    int64_t kmax = 0;
-    for (size_t g = 0; g + 1 < goff.size(); ++g)
-      kmax = std::max(kmax, goff[g + 1] - goff[g]);
-    if (kmax > kOrderedFoldChunk) {
-      if ((double)S * (double)NB * 9.0 <= kOrderedRowBudget) {
-        fold = false;
-        WB = NW = 0;
-      } else if (exact) {
-        return fail(OTSDB_E_CAPACITY,
-                    "exact-order dev: %lld x %lld bucket rows past the row "
-                    "budget", (long long)S, (long long)NB);
-      }
-    }
-  }
-  const bool cfold = cells && fold;
-  // verbatim storage rows: the single-window cells fold only (it checks
-  // what compaction would change; window boundaries it does not see)
-  if (c->verbatim && (!cfold || NW > 1)) return spec_miss(c);
-  // one chain per (group, bucket) up to kOrderedChunk members; partials for
-  // the merge across ranks (a group too large to hand on, dist.py) keep
-  // round 4's shorter chains, merged in order anyway
-  // the chained entry always takes the row path (its chains continue from
-  // the previous rank's states): past the row budget a clear E_CAPACITY
-  if (ginit && (double)S * (double)NB * 9.0 > kOrderedRowBudget)
-    return fail(OTSDB_E_CAPACITY,
-                "chained partials: %lld x %lld bucket rows past the row budget",
-                (long long)S, (long long)NB);
-  if (exact && mode == 1 && !ginit)
-    return fail(OTSDB_E_UNSUPPORTED,
-                "exact-order dev across ranks: hand the chains on "
-                "(otsdb_agg_partials_chained_device)");
-  otsdb_status rc = build_tiles(
-      c, goff, mode == 2,
-      fold ? (ordered ? kFoldChunk : kFoldChunkLarge) : kChunk,
-      ordered ? (fold ? kOrderedFoldChunk
-                      : (exact ? INT64_MAX
-                               : (mode == 1 && !ginit ? kOrderedChunkMerged
-                                                      : kOrderedChunk)))
-              : (fold ? kFoldChunk : 0));
+  Route R;
+  otsdb_status rc =
+      route_pipeline(c, spec, goff, P, S, mode, cells != nullptr,
+                     ginit != nullptr, &R);
+  if (rc) return rc;
+  const bool fold = R.fold, cfold = cells && fold;
+  rc = build_tiles(c, goff, mode == 2, R.chunk, R.whole_upto);
   if (rc) return rc;
   const Tiles T = tiles_of(c, G);
+  // the fold's windows and member contexts (foldplan.h); verbatim rows keep
+  // their one window
   P.fold_wb = 0;  // (P may come from an earlier pipeline run)
   P.fold_ctx = 0;
-  if (fold && OTSDB_FOLD_CTX) {
-    // tiles of up to 64 members load every member context at workgroup
-    // start (k_fold; ds_tu.hip drops it when the LDS would cost occupancy)
-    // (non-ordered: the largest tile, a group kept whole or one chunk of a
-    // larger one; ordered: bounded by its whole-group size)
-    int64_t tile_max = 0;
-    for (size_t g = 0; g + 1 < goff.size(); ++g) {
-      const int64_t k = goff[g + 1] - goff[g];
-      tile_max = std::max(
-          tile_max, ordered ? std::min(k, kOrderedFoldChunk)
-                            : (k <= kFoldChunk ? k : std::min(k, kFoldChunkLarge)));
-    }
-    if (tile_max > 0 && tile_max <= 64) P.fold_ctx = (int32_t)tile_max;
-  }
-  // few tiles (small queries, e.g. C1's 100 groups of 10 series): narrower
-  // fold windows give the grid more workgroups — each window's workgroup
-  // streams only that window's points (k_fold_prep hands it the context)
-  if (fold && !c->verbatim && T.T > 0 && NB > kFoldMinWindow &&
-      T.T * NW < kFoldMinBlocks) {
-    const int64_t want = (kFoldMinBlocks + T.T - 1) / T.T;  // windows
-    int64_t wb = (NB + want - 1) / want;
-    wb = (wb + 63) / 64 * 64;
-    if (wb < kFoldMinWindow) wb = kFoldMinWindow;
-    if (wb < WB) {
-      WB = wb;
-      NW = (NB + WB - 1) / WB;
-      P.fold_wb = (int32_t)WB;
-    }
+  int64_t WB = 0, NW = 0;
+  if (fold) {
+    const FoldPlan fp =
+        fold_plan(goff, T.T, NB, R.wb_cap, R.ordered, !c->verbatim);
+    WB = fp.WB;
+    NW = fp.NW;
+    P.fold_wb = fp.fold_wb;
+    P.fold_ctx = fp.fold_ctx;
   }
   // the bucket matrix (series rows) exists only off the fold path
   if (!fold && (double)S * (double)NB > 2.0e10)
@@ -1311,11 +1367,6 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
   const size_t rows = fold ? 0 : (size_t)S * NB;
   WinCtx* wc = nullptr;
   CellsFold CF{};
-  if (cfold) {
-    CF.C = *cells;
-    CF.series_row = series_row;
-    CF.wide = c->d_err + 1;
-  }
   auto carve = [&](char* base) {
     Carve cv{base};
     carve_series(cv, W, S);
@@ -1327,18 +1378,7 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
     W.out_emit = cv.take<uint8_t>((size_t)G * NB);
     W.counts = cv.take<int64_t>(G + 1);
     if (NW > 1) wc = cv.take<WinCtx>((size_t)S * (NW - 1));
-    if (cfold) {
-      CF.rlo = cv.take<int64_t>(S);
-      CF.vlo = cv.take<int64_t>(S);
-      CF.qw = cv.take<uint8_t>(S);
-      CF.vl0 = cv.take<uint8_t>(S);
-      CF.uf = cv.take<uint8_t>(S);
-      if (NW > 1) {
-        CF.wrlo = cv.take<int64_t>((size_t)S * (NW - 1));
-        CF.wvlo = cv.take<int64_t>((size_t)S * (NW - 1));
-        CF.wvl0 = cv.take<uint8_t>((size_t)S * (NW - 1));
-      }
-    }
+    if (cfold) carve_cells_fold(cv, CF, c, *cells, series_row, S, NW);
     if (two_level) carve_combine(cv, W, n_comb, NB);
     if (sel_large) carve_selection(cv, W, goff.back(), T.LG, NB, mode == 2);
     return cv.off + 256;
@@ -1371,8 +1411,6 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
   const bool rate_fused =
       P.sentinel && P.rate && !P.fill && !P.run_all && !c->rollup;
 
-  bool ok = true;
-  DsLaunch a = ds_args(c, P, B, W);
 #ifdef OTSDB_DEBUG_SYNC
   fprintf(stderr, "[otsdb] pipeline S=%lld NB=%lld fold=%d NW=%lld T=%lld G=%lld\n",
           (long long)S, (long long)NB, (int)fold, (long long)NW, (long long)T.T,
@@ -1381,82 +1419,23 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
   OTSDB_DBG(st, "setup");
   if (fold && S > 0 && NB > 0) {
     // downsample + contribution + aggregator in one ordered pass
-    ok = with_monoid(spec->ds_agg_id, [&](auto tag) {
+    DsLaunch a = ds_args(c, P, B, W);
+    fold_args(a, T, d_members, wc, NW, WB, W.tile_emit);
+    a.cf = CF;
+    a.partial = W.partial;
+    a.out_val = W.out_val;
+    a.out_emit = W.out_emit;
+    a.always_partial = mode == 1;
+    a.agg_id = spec->agg_id;
+    const bool ok = with_monoid(spec->ds_agg_id, [&](auto tag) {
       using M = decltype(tag);
-      {
-        StageTimer tm(c, 3);
-        if (cfold) {
-          a.cf = CF;
-          launch_cells<M>(DS_CELLS_PREP, a);
-          if (!c->cells_no_uni) launch_cells<M>(DS_CELLS_UNIFORM, a);
-          if (NW > 1) {
-            a.wc = wc;
-            a.NW = NW;
-            a.WB = WB;
-            launch_cells<M>(DS_CELLS_FOLD_PREP, a);
-          }
-        } else if (NW > 1 && S * (NW - 1) <= prep_fold_max()) {
-          a.wc = wc;
-          a.NW = NW;
-          a.WB = WB;
-          launch_ds<M>(DS_PREP_FOLD, a);
-        } else {
-          launch_ds<M>(DS_PREP, a);
-          if (NW > 1) {
-            a.wc = wc;
-            a.NW = NW;
-            a.WB = WB;
-            launch_ds<M>(DS_FOLD_PREP, a);
-          }
-        }
-      }
+      fold_prep<M>(c, a, cfold);
       StageTimer tm(c, 0);
-      a.n_tiles = T.T;
-      a.tg = T.tg;
-      a.tm0 = T.tm0;
-      a.tm1 = T.tm1;
-      a.single = T.single;
-      a.members = d_members;
-      a.wc = wc;
-      a.NW = NW;
-      a.WB = WB;
-      a.partial = W.partial;
-      a.tile_emit = W.tile_emit;
-      a.out_val = W.out_val;
-      a.out_emit = W.out_emit;
-      a.always_partial = mode == 1;
-      a.agg_id = spec->agg_id;
-      if (T.T > 0) {
-        if (cfold) {
-          // the fold with the qualifier width fixed at compile time (one
-          // copy of the member loop per kernel: 14 % faster on C2's cells
-          // than a width read per member).  k_cells_prep's bits 0 / 1: 4- /
-          // 2-byte series kept; both -> ERR_CELLS_GENERIC, and the engine
-          // rewrites the batch with one width (k_requal) and runs again
-          // k_cells_uniform's bit 2: some kept series is not uniform (or
-          // the uniform kernel already missed in this call): the general one
-          int widths = 3;
-          bool uniform = false;
-          if (hipMemcpyAsync(&c->h_small[2], c->d_err, 2 * sizeof(int),
-                             hipMemcpyDeviceToHost, st) == hipSuccess &&
-              hipStreamSynchronize(st) == hipSuccess) {
-            widths = (int)((c->h_small[2] >> 32) & 3);
-            uniform = !c->cells_no_uni && !((c->h_small[2] >> 32) & 4);
-          }
-          if (widths == 3) {
-            const int e = (int)(c->h_small[2] & 0xFFFFFFFF) | ERR_CELLS_GENERIC;
-            c->h_small[3] = e;
-            hipMemcpyAsync(c->d_err, &c->h_small[3], sizeof(int),
-                           hipMemcpyHostToDevice, st);
-          } else if (uniform) {
-            launch_cells<M>(widths == 1 ? DS_CELLS_FOLD4U : DS_CELLS_FOLD2U, a);
-            ++c->n_cells_uniform;
-          } else {
-            launch_cells<M>(widths == 1 ? DS_CELLS_FOLD4 : DS_CELLS_FOLD2, a);
-            ++c->n_cells_general;
-          }
-        }
-        else launch_ds<M>(DS_FOLD, a);
+      if (T.T == 0) return;
+      if (!cfold) {
+        launch_ds<M>(DS_FOLD, a);
+      } else if ((a.cells_variant = cells_fold_variant(c)) != 0) {
+        launch_cells<M>(DS_CELLS_FOLD, a);
       }
     });
     if (!ok) return fail(OTSDB_E_UNSUPPORTED, "downsampler %d", spec->ds_agg_id);
@@ -2943,18 +2922,15 @@ bool multi_folds(const otsdb_query_spec* s0, const Req& q, const Params& P,
   return multi_classes(q, P, cls, ci) == 1;
 }
 
-// The folded multi call: run_pipeline's fold branch with k_fold_multi in
-// k_fold's place — the single fold's tiles (groups up to kFoldChunk members
-// whole, larger ones in tiles of kFoldChunkLarge), windows of
-// fold_wb<MEnv>() buckets narrowed by the single fold's rule, the same prep
-// kernels — then k_combine<M> per output over the tiles of larger groups and
-// the compaction of every output.  No row matrix, no transform, no group
-// pass.
+// The folded multi call: k_fold_multi over the single fold's tiles
+// (fold_tiling), windows and member contexts (fold_plan over
+// fold_wb<MEnv>() buckets) after the single fold's prep (fold_prep), then
+// k_combine<M> per output over the tiles of larger groups and the
+// compaction of every output.  No row matrix, no transform, no group pass.
 // cells / series_row (as run_pipeline's): the members are streamed from
-// compacted columns — k_cells_prep, k_cells_uniform and k_cells_fold_prep in
-// the prep kernels' place, the cursors sized for THIS state's windows, and
-// k_fold_multi's cells variant chosen from the widths / uniform words as the
-// single cells fold chooses k_fold's.  The pass ends with the launches (the
+// compacted columns — the cursors sized for THIS state's windows, and
+// k_fold_multi's cells variant by cells_fold_variant, as the single cells
+// fold chooses k_fold's.  The pass ends with the launches (the
 // cells attempt loop reads the error word before anything is compacted);
 // multi_fold_finish compacts the outputs.
 struct MultiFoldRun {
@@ -2983,37 +2959,17 @@ otsdb_status multi_fold_pass(otsdb_ctx* c, const otsdb_query_spec* s0,
   multi_classes(q, P, cls, ci);
   P.interp = ci[0];
   P.sentinel = 0;
-  rc = build_tiles(c, goff, false, kFoldChunkLarge, kFoldChunk);
+  const FoldTiling ft = fold_tiling(false);
+  rc = build_tiles(c, goff, false, ft.chunk, ft.whole_upto);
   if (rc) return rc;
   const Tiles T = tiles_of(c, G);
-  int64_t WB = fold_wb<MEnv>();
-  int64_t NW = (NB + WB - 1) / WB;
-  P.fold_wb = 0;
-  P.fold_ctx = 0;
-  // the largest tile's member contexts preloaded (ds_tu.hip drops them when
-  // the LDS would cost occupancy), as for the single fold
+  const FoldPlan fp = fold_plan(goff, T.T, NB, fold_wb<MEnv>(), false, true);
+  const int64_t WB = fp.WB, NW = fp.NW;
+  P.fold_wb = fp.fold_wb;
+  P.fold_ctx = fp.fold_ctx;
   bool empty_group = false;
-  int64_t tile_max = 0;
-  for (int64_t g = 0; g < G; ++g) {
-    const int64_t k = goff[g + 1] - goff[g];
-    empty_group |= k == 0;
-    tile_max = std::max(tile_max,
-                        k <= kFoldChunk ? k : std::min(k, kFoldChunkLarge));
-  }
-  if (OTSDB_FOLD_CTX && tile_max > 0 && tile_max <= 64)
-    P.fold_ctx = (int32_t)tile_max;
-  // few tiles: narrower windows, the single fold's rule over this state's cap
-  if (T.T > 0 && NB > kFoldMinWindow && T.T * NW < kFoldMinBlocks) {
-    const int64_t want = (kFoldMinBlocks + T.T - 1) / T.T;  // windows
-    int64_t wb = (NB + want - 1) / want;
-    wb = (wb + 63) / 64 * 64;
-    if (wb < kFoldMinWindow) wb = kFoldMinWindow;
-    if (wb < WB) {
-      WB = wb;
-      NW = (NB + WB - 1) / WB;
-      P.fold_wb = (int32_t)WB;
-    }
-  }
+  for (int64_t g = 0; g < G && !empty_group; ++g)
+    empty_group = goff[g + 1] == goff[g];
   // which partials the tiles of larger groups leave
   FoldMultiArgs FM{};
   FM.n_out = q.n;
@@ -3028,11 +2984,6 @@ otsdb_status multi_fold_pass(otsdb_ctx* c, const otsdb_query_spec* s0,
   Work W;
   WinCtx* wc = nullptr;
   CellsFold CF{};
-  if (cells) {
-    CF.C = *cells;
-    CF.series_row = series_row;
-    CF.wide = c->d_err + 1;
-  }
   auto carve = [&](char* base) {
     Carve cv{base};
     carve_series(cv, W, S);
@@ -3046,18 +2997,7 @@ otsdb_status multi_fold_pass(otsdb_ctx* c, const otsdb_query_spec* s0,
       out_emit[i] = cv.take<uint8_t>((size_t)G * NB);
     }
     if (NW > 1) wc = cv.take<WinCtx>((size_t)S * (NW - 1));
-    if (cells) {  // (NW: this state's windows, not the single query's)
-      CF.rlo = cv.take<int64_t>(S);
-      CF.vlo = cv.take<int64_t>(S);
-      CF.qw = cv.take<uint8_t>(S);
-      CF.vl0 = cv.take<uint8_t>(S);
-      CF.uf = cv.take<uint8_t>(S);
-      if (NW > 1) {
-        CF.wrlo = cv.take<int64_t>((size_t)S * (NW - 1));
-        CF.wvlo = cv.take<int64_t>((size_t)S * (NW - 1));
-        CF.wvl0 = cv.take<uint8_t>((size_t)S * (NW - 1));
-      }
-    }
+    if (cells) carve_cells_fold(cv, CF, c, *cells, series_row, S, NW);
     if (two_level) carve_combine(cv, W, T.MG, NB);
     return cv.off + 256;
   };
@@ -3090,65 +3030,21 @@ otsdb_status multi_fold_pass(otsdb_ctx* c, const otsdb_query_spec* s0,
   // output below is written by the fold or by k_combine)
   if (S > 0 && NB > 0 && T.T > 0) {
     DsLaunch a = ds_args(c, P, B, W);
+    fold_args(a, T, d_members, wc, NW, WB, W.tile_emit);
+    a.cf = CF;
+    a.fm = &FM;
     const bool ok = with_monoid(s0->ds_agg_id, [&](auto tag) {
       using M = decltype(tag);
-      {
-        StageTimer tm(c, 3);
-        a.wc = wc;
-        a.NW = NW;
-        a.WB = WB;
-        if (cells) {
-          a.cf = CF;
-          launch_cells<M>(DS_CELLS_PREP, a);
-          if (!c->cells_no_uni) launch_cells<M>(DS_CELLS_UNIFORM, a);
-          if (NW > 1) launch_cells<M>(DS_CELLS_FOLD_PREP, a);
-        } else if (NW > 1 && S * (NW - 1) <= prep_fold_max()) {
-          launch_ds<M>(DS_PREP_FOLD, a);
-        } else {
-          launch_ds<M>(DS_PREP, a);
-          if (NW > 1) launch_ds<M>(DS_FOLD_PREP, a);
-        }
-      }
+      fold_prep<M>(c, a, cells != nullptr);
       StageTimer tm(c, 0);
-      a.n_tiles = T.T;
-      a.tg = T.tg;
-      a.tm0 = T.tm0;
-      a.tm1 = T.tm1;
-      a.single = T.single;
-      a.members = d_members;
-      a.tile_emit = W.tile_emit;
-      a.fm = &FM;
       if (!cells) {
         launch_ds<M>(DS_FOLD_MULTI, a);
-        ++c->n_multi_fold;
-        return;
-      }
-      // the kernel with the qualifier width fixed, uniform or general: the
-      // single cells fold's choice (run_pipeline) from k_cells_prep's widths
-      // (bits 0 / 1: 4- / 2-byte series kept; both: ERR_CELLS_GENERIC, the
-      // attempt loop rewrites the columns) and k_cells_uniform's bit 2
-      int widths = 3;
-      bool uniform = false;
-      if (hipMemcpyAsync(&c->h_small[2], c->d_err, 2 * sizeof(int),
-                         hipMemcpyDeviceToHost, st) == hipSuccess &&
-          hipStreamSynchronize(st) == hipSuccess) {
-        widths = (int)((c->h_small[2] >> 32) & 3);
-        uniform = !c->cells_no_uni && !((c->h_small[2] >> 32) & 4);
-      }
-      if (widths == 3) {
-        const int e = (int)(c->h_small[2] & 0xFFFFFFFF) | ERR_CELLS_GENERIC;
-        c->h_small[3] = e;
-        hipMemcpyAsync(c->d_err, &c->h_small[3], sizeof(int),
-                       hipMemcpyHostToDevice, st);
-      } else if (uniform) {
-        launch_cells<M>(widths == 1 ? DS_CELLS_MULTI4U : DS_CELLS_MULTI2U, a);
-        ++c->n_cells_uniform;
-        ++c->n_multi_fold;
+      } else if ((a.cells_variant = cells_fold_variant(c)) != 0) {
+        launch_cells<M>(DS_CELLS_MULTI, a);
       } else {
-        launch_cells<M>(widths == 1 ? DS_CELLS_MULTI4 : DS_CELLS_MULTI2, a);
-        ++c->n_cells_general;
-        ++c->n_multi_fold;
+        return;  // mixed widths: the attempt loop rewrites the columns
       }
+      ++c->n_multi_fold;
     });
     if (!ok) return fail(OTSDB_E_UNSUPPORTED, "downsampler %d", s0->ds_agg_id);
     ++c->n_multi_ds;

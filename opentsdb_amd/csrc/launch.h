@@ -2,8 +2,10 @@
 // kernels templated on the DOWNSAMPLING monoid.  Those kernels (k_prep, the
 // ring k_bucketize_k, the rate-fused one, k_bucketize_cells, k_fold_prep and
 // the ordered group fold k_fold x every aggregator, k_fold_multi over the
-// envelope state) are compiled in one translation unit per downsampling
-// monoid (ds_tu.hip), in parallel.
+// envelope state; from compacted columns the cells prep kernels and the four
+// cells variants of either fold) are compiled in two translation units per
+// downsampling monoid (ds_tu.hip), in parallel.  How a fold is cut into
+// tiles and windows is foldplan.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,8 +36,10 @@ struct WinCtx {
   double next_val;
 };
 
-// A cells fold (k_cells_prep -> k_fold<..., CELLS = 1>, cellfold.hip): the
-// compacted columns and what the prep derives per series.  A series' points
+// A cells fold (k_cells_prep -> k_fold / k_fold_multi<..., CELLS>,
+// cellfold.hip; CELLS = 2 / 4: the general member walker over 2- / 4-byte
+// qualifiers, 10 / 12: the uniform one): the compacted columns and what the
+// prep derives per series.  A series' points
 // are numbered by qualifier: point p's qualifier sits at byte
 // qual_off[first row] + qw * p (rows are contiguous in the pools).
 struct CellsFold {
@@ -104,22 +108,18 @@ enum DsKernel {
   DS_FOLD_PREP,  // k_fold_prep: window boundaries of the ordered fold
   DS_FOLD,       // k_fold: downsample + contribution + ordered aggregator
   DS_CELLS_PREP, // k_cells_prep: bounds / cursors of a cells fold
-  DS_CELLS_FOLD, // (unused: a batch whose kept series mix qualifier widths
-                 // is rewritten with one width, k_requal)
+  DS_CELLS_FOLD, // k_fold from compacted columns, the kernel of
+                 // DsLaunch.cells_variant: the kept series' one qualifier
+                 // width a compile-time constant (a batch that mixes widths
+                 // is rewritten with one, k_requal), the general or the
+                 // uniform member walker (fold_member_cells_u)
   DS_CELLS_FOLD_PREP, // k_cells_fold_prep: window boundaries of a cells fold
-  DS_CELLS_FOLD2, // the cells fold of a batch whose kept series all have
-                  // 2-byte qualifiers (the width a compile-time constant)
-  DS_CELLS_FOLD4, // ... all 4-byte ones
   DS_PREP_FOLD,   // k_prep_fold: k_prep + k_fold_prep in one launch
   DS_CELLS_UNIFORM, // k_cells_uniform: which kept series are uniform
-  DS_CELLS_FOLD2U,  // the uniform cells fold (fold_member_cells_u), 2-byte
-  DS_CELLS_FOLD4U,  // ... 4-byte qualifiers
   DS_FOLD_MULTI,    // k_fold_multi: the fold over the envelope state, one
                     // pass for every output of a multi-aggregator call
-  DS_CELLS_MULTI2,  // k_fold_multi from compacted columns (launch_cells):
-  DS_CELLS_MULTI4,  // the general member walker, 2- / 4-byte qualifiers
-  DS_CELLS_MULTI2U, // ... the uniform one (fold_member_cells_u)
-  DS_CELLS_MULTI4U
+  DS_CELLS_MULTI    // k_fold_multi from compacted columns (launch_cells),
+                    // the kernel of DsLaunch.cells_variant as DS_CELLS_FOLD
 };
 
 // What a multi-aggregator fold (k_fold_multi, foldmulti.hip) finishes from
@@ -150,7 +150,7 @@ struct DsLaunch {
   // DS_CELLS
   CellsDev cells;
   const int64_t* series_row;
-  // DS_FOLD_PREP / DS_FOLD
+  // the folds and their prep kernels (DS_*FOLD*, DS_*MULTI): windows, tiles
   WinCtx* wc;
   int64_t NW, WB;
   int64_t n_tiles;
@@ -163,10 +163,13 @@ struct DsLaunch {
   uint8_t* out_emit;
   int always_partial;
   int agg_id;
-  // DS_CELLS_PREP / DS_CELLS_FOLD
+  // launch_cells' kernels (DS_CELLS_PREP ... DS_CELLS_MULTI)
   CellsFold cf;
-  // DS_FOLD_MULTI / DS_CELLS_MULTI* (beside DS_FOLD's tiles, windows and
-  // tile_emit; the cells ones with cf)
+  // DS_CELLS_FOLD / DS_CELLS_MULTI: the kernel's CELLS template value — 2 / 4:
+  // 2- / 4-byte qualifiers, the general member walker; 10 / 12: the uniform
+  int cells_variant;
+  // DS_FOLD_MULTI / DS_CELLS_MULTI (beside DS_FOLD's tiles, windows and
+  // tile_emit)
   const FoldMultiArgs* fm;
 };
 

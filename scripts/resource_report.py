@@ -2,7 +2,8 @@
 (hipcc -Rpass-analysis=kernel-resource-usage, build.py's flags), for this tree
 and, with --before, for another checkout of the project (the parent commit):
 which kernels exist on both sides, whether their figures are identical, and
-the figures of the kernels whose names match --new.
+the figures of the kernels whose names match --new.  --ds-monoids compares
+the ds_tu.hip units of those downsampling monoids as well, both parts.
 
     python -m scripts.resource_report --before PATH/TO/PARENT/CHECKOUT \
         --new k_rr_ --out profiles/rollup_rows_resources.json
@@ -23,11 +24,11 @@ FIELDS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]",
           "VGPRs Spill", "LDS Size [bytes/block]")
 
 
-def report(root, unit="engine.hip"):
+def report(root, unit="engine.hip", defines=()):
     """{demangled kernel name: {field: value}} of one translation unit."""
     from opentsdb_amd import build
     src = os.path.join(root, "opentsdb_amd", "csrc", unit)
-    cmd = [build.HIPCC] + build.FLAGS + [
+    cmd = [build.HIPCC] + build.FLAGS + ["-D" + d for d in defines] + [
         "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c",
         "-o", os.devnull, src]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
@@ -47,31 +48,40 @@ def report(root, unit="engine.hip"):
     return {d or n: out[n] for n, d in zip(names, dem)}
 
 
+def compare(before, after):
+    return {"kernels_before": len(before), "kernels_after": len(after),
+            "kernels_only_before": sorted(set(before) - set(after)),
+            "kernels_only_after": sorted(set(after) - set(before)),
+            "kernels_with_other_figures": sorted(
+                k for k in before if k in after and before[k] != after[k])}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--before", default=None, help="the parent's checkout")
     ap.add_argument("--new", default="k_rr_",
                     help="substring of the new kernels' names")
+    ap.add_argument("--ds-monoids", default="",
+                    help="comma-separated OTSDB_DS_MONOID values")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     after = report(ROOT)
     doc = {"arch": "gfx950",
            "source": "hipcc " + " ".join(__import__(
                "opentsdb_amd.build", fromlist=["FLAGS"]).FLAGS[1:5]) +
-           " -Rpass-analysis=kernel-resource-usage: engine.hip (the one unit "
-           "that includes rollup_rows.hip; the ds_tu.hip and rollup.hip units "
-           "do not, and are built from unchanged sources with unchanged "
-           "flags); before = the parent commit",
+           " -Rpass-analysis=kernel-resource-usage, one translation unit per "
+           "entry below; before = the parent commit",
            "new": {k: v for k, v in after.items() if a.new in k}}
     if a.before:
         before = report(a.before)
         old = {k: v for k, v in after.items() if a.new not in k}
-        doc["engine.hip"] = {
-            "kernels_before": len(before), "kernels_after": len(old),
-            "kernels_only_before": sorted(set(before) - set(old)),
-            "kernels_only_after": sorted(set(old) - set(before)),
-            "kernels_with_other_figures": sorted(
-                k for k in before if k in old and before[k] != old[k])}
+        doc["engine.hip"] = compare(before, old)
+        for m in filter(None, a.ds_monoids.split(",")):
+            for part in (0, 1):
+                d = ("OTSDB_DS_MONOID=" + m, "OTSDB_DS_PART=%d" % part)
+                doc["ds_tu.hip " + " ".join("-D" + x for x in d)] = compare(
+                    report(a.before, "ds_tu.hip", d),
+                    report(ROOT, "ds_tu.hip", d))
     print(json.dumps(doc, indent=1))
     if a.out:
         with open(a.out, "w") as f:
