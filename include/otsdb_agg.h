@@ -50,12 +50,13 @@ typedef enum {
   OTSDB_E_ILLEGAL_ARGUMENT = 3,
   /* NoSuchElementException: unknown aggregator (Aggregators.java:222-228). */
   OTSDB_E_NO_SUCH_ELEMENT = 4,
-  /* Valid in the reference but not implemented by this engine (histograms,
-   * scalar fill, rollup avg downsampled with another function, rollup
-   * queries without a downsampler or over per-series calendar anchors): the
-   * Java side keeps its own iterators for such queries.  Also what the
-   * reference itself refuses with UnsupportedOperationException (a rollup
-   * table's dev).                                                           */
+  /* Valid in the reference but not implemented by this engine (scalar fill,
+   * rollup avg downsampled with another function, rollup queries without a
+   * downsampler or over per-series calendar anchors; histogram queries
+   * without a downsampler, with "0all" or a calendar interval, over rollup
+   * tables, or past the limits of otsdb_hist_*): the Java side keeps its own
+   * iterators for such queries.  Also what the reference itself refuses with
+   * UnsupportedOperationException (a rollup table's dev).                   */
   OTSDB_E_UNSUPPORTED = 5,
   /* HIP runtime failure / out of device memory.                            */
   OTSDB_E_DEVICE = 6,
@@ -894,13 +895,145 @@ otsdb_status otsdb_agg_run_rollup_rows(
     const otsdb_rollup_table* table, int32_t rollup_agg_id,
     const otsdb_batch* batch, otsdb_result* out);
 
+/* ---- histogram queries --------------------------------------------------- */
+/* The query over histogram data points (2.4): the group's members are
+ * downsampled and summed as histograms and the percentiles are read off the
+ * sums — HistogramSpanGroup.iterator (HistogramSpanGroup.java:347-350) with
+ * one HistogramDataPointsToDataPointsAdaptor per percentile
+ * (TsdbQuery.java:1324-1333), aggregated ONCE here for every percentile.
+ *
+ * Per series (HistogramDownsampler.java:129-149, :195-377): the seek is the
+ * first point >= align(start_ms + interval - 1), align(t) = t - t % interval;
+ * bucket b holds the points of [align(t), align(t) + interval), its timestamp
+ * is the bucket start; no fill policy, no empty bucket (HistogramSpan.java:
+ * 554-563 ignores the fill); a bucket is read to its end even past end_ms.
+ * With spec->ds_agg_id == OTSDB_AGG_SUM (the function string is "sum",
+ * DownsamplingSpecification.java:153-157) the bucket is the sum of its
+ * histograms; with any other function the reference's aggregate(x, null)
+ * does nothing and the bucket is its FIRST histogram alone — reproduced.
+ * Across a group's members (HistogramAggregationIterator.java:240-287): the
+ * output timestamps are the union of the members' bucket timestamps <=
+ * end_ms, the value at each the SUM of the members with a bucket exactly
+ * there; nothing is interpolated.  spec->agg_id, interp, fill and the rate
+ * fields are ignored, as the reference ignores them (TsdbQuery.java:1200,
+ * :1277).  Sums are Java long additions (they wrap), per (lower, upper) key,
+ * underflow and overflow likewise (SimpleHistogram.java:246-261).
+ *
+ * Percentile p, a float widened to double (SimpleHistogram.java:124-164):
+ * p < 1.0 || p > 100.0 gives -1.0; int bucketSum is the wrapping 32-bit sum
+ * of every count's intValue(); walking the keys in order, long running +=
+ * intValue() and area = running * 100.0 / bucketSum (separate double
+ * operations); the first key with area >= p gives (double)((lower + upper) /
+ * 2) in float arithmetic; no such key (bucketSum == 0 with NaN areas, a NaN
+ * p) gives 0.0.  Underflow and overflow take no part.
+ *
+ * Columns.  The batch supplies offsets, ts_ms and the groups (val, is_float,
+ * series_float are not read and may be NULL).  lower / upper: the query's
+ * bucket schema, HOST memory on every entry, n_bins = K keys strictly
+ * ascending in TreeMap order — Float.compare on lower, then on upper
+ * (HistogramDataPoint.java:147-165); anything else: OTSDB_E_ILLEGAL_ARGUMENT.
+ * counts: [n_points][K + 2] int64 row-major, columns K and K + 1 the
+ * underflow and overflow; one point is one contiguous record (8-byte aligned;
+ * 16-byte loads when K is even and the matrix 16-byte aligned).  A HOST
+ * pointer for otsdb_hist_run, a DEVICE pointer for the _device entries.
+ * Decoding the stored blobs stays with the caller (codecs are plugins,
+ * HistogramCodecManager; the Java side holds decoded objects).  The schema is
+ * the union of the keys of every histogram of the query; a histogram that
+ * lacks a key passes 0 there.  A zero-count key can never be the one a
+ * percentile picks — its area equals its predecessor's, which did not
+ * qualify, or at the start is +-0.0 or NaN, below every valid p — so the
+ * padding changes no percentile.  The merged-counts output cannot tell a key
+ * absent from every member from one whose counts sum to 0.
+ *
+ * Result: group g's points are [offsets[g], offsets[g + 1]); ts [capacity];
+ * pct_val [n_pct][capacity] doubles, percentile q of point i at
+ * pct_val[q * capacity + i] (every percentile shares offsets and ts); counts,
+ * optional (NULL skips it), [capacity][K + 2]: the merged histograms
+ * (HistogramBucketDataPointsAdaptor, show_histogram_buckets).
+ *
+ * Limits: K < 1, a NULL schema, n_pct < 0, n_pct == 0 with a NULL
+ * result->counts, start_ms < 0: OTSDB_E_ILLEGAL_ARGUMENT.  K + 2 >
+ * OTSDB_HIST_MAX_ROW, n_pct > OTSDB_HIST_MAX_PCT, ds_interval_ms == 0 (the
+ * raw timestamp union), run_all, use_calendar, a grid whose first bucket is
+ * timestamp 0 (the reference's "end reached" mark): OTSDB_E_UNSUPPORTED.  A
+ * dense array n_groups x n_buckets x (K + 2) x 8 bytes past
+ * OTSDB_HIST_DENSE_BYTES: OTSDB_E_CAPACITY.  All of these are decided before
+ * any device work.  A result capacity too small: OTSDB_E_CAPACITY with the
+ * offsets whole (otsdb_agg_run's contract).  The cells, multi and panel
+ * entries do not take histograms.                                           */
+#define OTSDB_HIST_MAX_ROW 256
+#define OTSDB_HIST_MAX_PCT 16
+#define OTSDB_HIST_DENSE_BYTES (8LL << 30)
+typedef struct {
+  int32_t n_bins;        /* K                                               */
+  const float* lower;    /* [K] HOST                                        */
+  const float* upper;    /* [K] HOST                                        */
+  const int64_t* counts; /* [n_points][K + 2]                               */
+} otsdb_hist_columns;
+
+typedef struct {
+  int64_t capacity;
+  int64_t* offsets;  /* [G+1]                                               */
+  int64_t* ts;       /* [capacity]                                          */
+  double* pct_val;   /* [n_pct][capacity]; may be NULL when n_pct == 0      */
+  int64_t* counts;   /* [capacity][K + 2] or NULL                           */
+} otsdb_hist_result;
+
+/* n_buckets, max_out_points (groups x buckets) and workspace_bytes, as
+ * otsdb_agg_plan returns them; the checks above.  ctx is not read.         */
+otsdb_status otsdb_hist_plan(otsdb_ctx* ctx, const otsdb_query_spec* spec,
+                             const otsdb_batch* batch,
+                             const otsdb_hist_columns* hist, otsdb_sizes* out);
+/* Host pointers throughout; synchronous.                                   */
+otsdb_status otsdb_hist_run(otsdb_ctx* ctx, const otsdb_query_spec* spec,
+                            const otsdb_batch* batch,
+                            const otsdb_hist_columns* hist,
+                            const float* percentiles, int32_t n_pct,
+                            otsdb_hist_result* out);
+/* Device pointers (schema and percentiles stay HOST); returns after the
+ * result is complete on the device.                                        */
+otsdb_status otsdb_hist_run_device(otsdb_ctx* ctx, const otsdb_query_spec* spec,
+                                   const otsdb_batch* batch,
+                                   const otsdb_hist_columns* hist,
+                                   const float* percentiles, int32_t n_pct,
+                                   otsdb_hist_result* out, void* hip_stream);
+/* The two halves of the run, for series-sharded ranks.  partials: the local
+ * shard's dense sums, DEVICE int64 [G][n_buckets][K + 2] and uint8 emit
+ * [G][n_buckets] (1: some local member has a bucket there), every cell
+ * written (0 where nothing was added).  The ranks' arrays combine by plain
+ * integer addition (all-reduce SUM on dense, MAX on emit) in any order: the
+ * same bits as one rank over every series.  finalize: percentiles and the
+ * compacted result from such arrays; hist supplies the schema (counts is not
+ * read); n_buckets must be the plan's.                                     */
+otsdb_status otsdb_hist_partials_device(otsdb_ctx* ctx,
+                                        const otsdb_query_spec* spec,
+                                        const otsdb_batch* batch,
+                                        const otsdb_hist_columns* hist,
+                                        int64_t* dense, uint8_t* emit,
+                                        void* hip_stream);
+otsdb_status otsdb_hist_finalize_device(otsdb_ctx* ctx,
+                                        const otsdb_query_spec* spec,
+                                        const otsdb_hist_columns* hist,
+                                        int64_t n_groups, int64_t n_buckets,
+                                        const int64_t* dense,
+                                        const uint8_t* emit,
+                                        const float* percentiles,
+                                        int32_t n_pct, otsdb_hist_result* out,
+                                        void* hip_stream);
+/* Host-only planning: the buckets one workgroup of the histogram fold holds
+ * for rows of n_bins + 2 counts (0 outside the limits).  Decides speed, not
+ * results; tests take the window edges from it.                            */
+int32_t otsdb_hist_window(int32_t n_bins);
+
 /* ---- stage timing (bench roofline) ------------------------------------- */
 /* When enabled, every query records HIP events around its pipeline stages
  * on the query's stream.  otsdb_prof_read returns, per stage, the summed
  * milliseconds and the number of launches since the last reset:
  * [0] k_bucketize  [1] k_transform  [2] k_group+k_combine  [3] k_prep
  * [4] k_compact+k_scan; [5] query-time compaction, [6] span assembly, [7] the
- * decode into the context's columnar buffer (compacted cells, rollup rows).
+ * decode into the context's columnar buffer (compacted cells, rollup rows);
+ * histogram queries: [8] k_hist_prep + k_hist_fold, [9] k_hist_combine,
+ * [10] k_hist_percentiles, [11] their compaction (n up to 12).
  * Synchronises the stream.                                                  */
 otsdb_status otsdb_prof_enable(otsdb_ctx* ctx, int enable);
 otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
@@ -923,7 +1056,9 @@ otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
  * out[12]: multi-aggregator folds launched by the last otsdb_agg_*_multi*
  * call (OTSDB_SPEC_MULTI_FOLD on an eligible request: 1, else 0;
  * OTSDB_SPEC_CELLS_MULTI_FOLD: one per cells fold launched, 2 after a uniform
- * miss).                                                                    */
+ * miss).  Of the last otsdb_hist_* call: out[13] k_hist_fold launches (one
+ * aggregation, whatever the number of percentiles), out[14] percentile
+ * passes over the dense sums (1, or 0 when n_pct == 0).                     */
 otsdb_status otsdb_ctx_counters(otsdb_ctx* ctx, int64_t* out, int n);
 /* Test hook: the one-pass compaction's epoch (1 .. 2^24 - 1, forward only)
  * the context's next call increments, so tests can drive it to its wrap.  */

@@ -132,6 +132,31 @@ class RollupTable(C.Structure):
     ]
 
 
+class HistColumns(C.Structure):
+    """otsdb_hist_columns: the bucket schema (host floats) and the [N][K + 2]
+    count matrix."""
+    _fields_ = [
+        ("n_bins", C.c_int32),
+        ("lower", C.c_void_p),
+        ("upper", C.c_void_p),
+        ("counts", C.c_void_p),
+    ]
+
+
+class HistResult(C.Structure):
+    _fields_ = [
+        ("capacity", C.c_int64),
+        ("offsets", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("pct_val", C.c_void_p),
+        ("counts", C.c_void_p),
+    ]
+
+
+HIST_MAX_ROW = 256  # OTSDB_HIST_MAX_ROW
+HIST_MAX_PCT = 16   # OTSDB_HIST_MAX_PCT
+
+
 class GenSpec(C.Structure):
     _fields_ = [
         ("seed", C.c_uint64),
@@ -172,6 +197,9 @@ EXPORTS = [
     "otsdb_agg_run_rollup_device", "otsdb_agg_run_rollup",
     "otsdb_rollup_decode_rows_device", "otsdb_agg_run_rollup_rows_device",
     "otsdb_agg_run_rollup_rows",
+    "otsdb_hist_plan", "otsdb_hist_run", "otsdb_hist_run_device",
+    "otsdb_hist_partials_device", "otsdb_hist_finalize_device",
+    "otsdb_hist_window",
 ]
 
 MULTI_MAX = 32  # OTSDB_MULTI_MAX
@@ -325,6 +353,25 @@ def load(path=None):
         lib.otsdb_agg_run_rollup_rows_device.restype = C.c_int
         lib.otsdb_agg_run_rollup_rows.argtypes = [vp, PS, PW, PT, i32, PB, PR]
         lib.otsdb_agg_run_rollup_rows.restype = C.c_int
+    # histogram queries: (ctx, spec, batch, hist, sizes), (ctx, spec, batch,
+    # hist, percentiles, n_pct, result [, stream]), (ctx, spec, batch, hist,
+    # dense, emit, stream), (ctx, spec, hist, G, n_buckets, dense, emit,
+    # percentiles, n_pct, result, stream)
+    if hasattr(lib, "otsdb_hist_run"):
+        PH, PHR = C.POINTER(HistColumns), C.POINTER(HistResult)
+        lib.otsdb_hist_plan.argtypes = [vp, PS, PB, PH, C.POINTER(Sizes)]
+        lib.otsdb_hist_plan.restype = C.c_int
+        lib.otsdb_hist_run.argtypes = [vp, PS, PB, PH, vp, i32, PHR]
+        lib.otsdb_hist_run.restype = C.c_int
+        lib.otsdb_hist_run_device.argtypes = [vp, PS, PB, PH, vp, i32, PHR, vp]
+        lib.otsdb_hist_run_device.restype = C.c_int
+        lib.otsdb_hist_partials_device.argtypes = [vp, PS, PB, PH, vp, vp, vp]
+        lib.otsdb_hist_partials_device.restype = C.c_int
+        lib.otsdb_hist_finalize_device.argtypes = [vp, PS, PH, i64, i64, vp, vp,
+                                                   vp, i32, PHR, vp]
+        lib.otsdb_hist_finalize_device.restype = C.c_int
+        lib.otsdb_hist_window.argtypes = [i32]
+        lib.otsdb_hist_window.restype = i32
     # bound only on the ABI it was added to: a stale library of another
     # version must not hand out a symbol of other arguments
     if lib.otsdb_abi_version() == 6 and hasattr(lib, "otsdb_sel_retarget"):

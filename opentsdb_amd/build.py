@@ -4,8 +4,8 @@ hipcc cross-compiles without a GPU, so this runs in the CPU container; the
 resulting .so travels to the GPU box with the repository snapshot.
 
 The device code is split over translation units compiled in parallel: the
-engine (host code, the non-template kernels — storage rows and rollup rows
-among them — and the aggregator-templated ones), two units per downsampling monoid (csrc/ds_tu.hip with
+engine (host code, the non-template kernels — storage rows, rollup rows and
+the histogram query's among them — and the aggregator-templated ones), two units per downsampling monoid (csrc/ds_tu.hip with
 -DOTSDB_DS_MONOID=n: the downsample / ordered-fold kernels of that monoid,
 and with -DOTSDB_DS_PART=1 the cells fold of that monoid) and csrc/rollup.hip
 (the prep and ring kernels of the two rollup states, nothing else).
@@ -94,7 +94,8 @@ def build(force=False, verbose=False, jobs=None, defines=(), out=None):
     # kernels.hip, decode.hip, fold.hip, cellfold.hip and the headers)
     engine_only = ("engine.hip", "select.hip", "raw.hip", "rows.hip",
                    "rollup_rows.hip", "calendar.hip", "compact.hip",
-                   "multi.hip", "panel.hip", "foldplan.h")
+                   "multi.hip", "panel.hip", "hist.hip", "histplan.h",
+                   "foldplan.h")
 
     def stale(u):
         src, extra, obj = u

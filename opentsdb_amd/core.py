@@ -245,6 +245,7 @@ class DownsamplingSpecification:
             self.use_calendar = False
             self.run_all = False
             self.timezone = None
+            self.histogram_aggregation = None  # (the ctor leaves it null)
             return
         if specification is None:
             raise IllegalArgumentException(
@@ -273,6 +274,11 @@ class DownsamplingSpecification:
             self.interval = DateTime.parseDuration(parts[0])
             self.use_calendar = False
             self.string_interval = parts[0]
+        # getHistogramAggregation (DownsamplingSpecification.java:153-157):
+        # SUM iff the function is "sum"; anything else leaves a histogram
+        # bucket its first point alone (opentsdb_amd.histogram)
+        self.histogram_aggregation = ("SUM" if parts[1].lower() == "sum"
+                                      else None)
         try:
             self.function = Aggregators.get(parts[1])
         except NoSuchElementException:

@@ -26,6 +26,8 @@ finalize (otsdb_agg_partials_multi_device / _finalize_multi_device);
 several medians / percentiles share one selection session
 (otsdb_sel_retarget, run_sharded_select_multi).
 """
+import ctypes as C
+
 import numpy as np
 
 from . import abi
@@ -617,6 +619,46 @@ def run_sharded_multi(engine, spec, aggs, dbatch, n_groups_global,
     for j, i in enumerate(todo):
         results[i] = ShardedResult(plan.local, local[j], plan.merge, merged[j])
     return results
+
+
+def run_sharded_hist(engine, spec, dhist, dbatch, percentiles, n_groups,
+                     want_counts=False, group=None):
+    """The histogram query over series-sharded ranks: every rank sums its
+    shard (otsdb_hist_partials_device), the dense int64 sums are all-reduced
+    (SUM) and the emit flags (MAX), and every rank finalises the same arrays
+    (otsdb_hist_finalize_device).  No protocol: the partials are plain
+    wrapping integer sums, so the result is the single run's bit for bit in
+    any order.  dbatch's groups span all `n_groups` global groups (empty where
+    the rank holds no member).  Without an initialised process group the rank
+    is the whole world.  Returns a DeviceHistResult."""
+    import torch
+    import torch.distributed as tdist
+    from .engine import (DeviceHistResult, hist_finalize_device,
+                         hist_partials_device)
+    from .histogram import percentile_spec
+    if dbatch.n_groups != n_groups:
+        raise ValueError("the shard's groups must span the %d global groups"
+                         % n_groups)
+    p = percentile_spec(percentiles)
+    sz = abi.Sizes()
+    b, h = dbatch.as_abi(), dhist.as_abi()
+    engine._check(engine.lib.otsdb_hist_plan(
+        engine.ctx, C.byref(spec), C.byref(b), C.byref(h), C.byref(sz)))
+    nb = int(sz.n_buckets)
+    dev = dbatch.offsets.device
+    dense = torch.zeros((n_groups, max(nb, 1), dhist.n_bins + 2),
+                        dtype=torch.int64, device=dev)
+    emit = torch.zeros((n_groups, max(nb, 1)), dtype=torch.uint8, device=dev)
+    hist_partials_device(engine, spec, dbatch, dhist, dense, emit)
+    if tdist.is_available() and tdist.is_initialized() and \
+            tdist.get_world_size(group) > 1:
+        all_reduce(dense, "sum", group)
+        all_reduce(emit, "max", group)
+    res = DeviceHistResult(torch, n_groups, n_groups * nb, dhist.n_bins,
+                           len(p), want_counts, dev)
+    hist_finalize_device(engine, spec, dhist, n_groups, nb, dense, emit, p,
+                         res)
+    return res
 
 
 def shard_host_batch(hb, world, rank, by_points=True):

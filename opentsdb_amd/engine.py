@@ -367,6 +367,49 @@ class Engine:
             C.byref(b), rs))
         return points()[0]
 
+    def hist_counters(self):
+        """Of the last histogram call (otsdb_ctx_counters [13..14]):
+        k_hist_fold launches (one aggregation for every percentile) and
+        percentile passes over the dense sums."""
+        out = self._counters(15)
+        return dict(fold_launches=int(out[13]), percentile_passes=int(out[14]))
+
+    def plan_hist(self, spec, batch, hist):
+        sz = abi.Sizes()
+        h = hist.as_abi()
+        self._check(self.lib.otsdb_hist_plan(self.ctx, C.byref(spec),
+                                             C.byref(batch.as_abi()),
+                                             C.byref(h), C.byref(sz)))
+        return sz
+
+    def run_hist(self, spec, batch, hist, percentiles, want_counts=False):
+        """A histogram query (host arrays): `batch` supplies the series'
+        timestamps and the groups (its values are not read), `hist` is a
+        histogram.HistColumns (schema and the [N][K + 2] counts) and
+        `percentiles` the percentiles, held as float32.  The members are
+        downsampled and summed once; returns one HistPoints per group with
+        every percentile (and the merged counts when want_counts)."""
+        from .histogram import percentile_spec
+        p = percentile_spec(percentiles)
+        sz = self.plan_hist(spec, batch, hist)
+        cap = max(1, int(sz.max_out_points))
+        G, R, n = batch.n_groups, hist.n_bins + 2, len(p)
+        offs = np.zeros(G + 1, np.int64)
+        ts = np.zeros(cap, np.int64)
+        pct = np.zeros((max(n, 1), cap), np.float64)
+        cnt = np.zeros((cap, R), np.int64) if want_counts else None
+        r = abi.HistResult(cap, offs.ctypes.data, ts.ctypes.data,
+                           pct.ctypes.data if n else None,
+                           None if cnt is None else cnt.ctypes.data)
+        b, h = batch.as_abi(), hist.as_abi()
+        self._check(self.lib.otsdb_hist_run(
+            self.ctx, C.byref(spec), C.byref(b), C.byref(h),
+            p.ctypes.data if n else None, n, C.byref(r)))
+        return [HistPoints(ts[offs[g]:offs[g + 1]],
+                           pct[:n, offs[g]:offs[g + 1]],
+                           None if cnt is None else cnt[offs[g]:offs[g + 1]])
+                for g in range(G)]
+
     def plan_multi(self, spec, aggs, batch, interps=None):
         n, ids, it = multi_args(aggs, interps)
         sz = abi.Sizes()
@@ -420,6 +463,17 @@ class Engine:
             self.ctx, C.byref(spec), n, ds.ctypes.data, ids.ctypes.data,
             it.ctypes.data, C.byref(b), rs))
         return points()
+
+
+class HistPoints:
+    """One group's histogram result: ts [n], pct [P][n] (percentile q of
+    point i at pct[q, i]) and the merged counts [n][K + 2] or None."""
+
+    def __init__(self, ts, pct, counts):
+        self.ts, self.pct, self.counts = ts, pct, counts
+
+    def __len__(self):
+        return len(self.ts)
 
 
 class DeviceBatch:
@@ -688,3 +742,87 @@ def finalize_multi_device(engine, spec, aggs, n_groups, n_buckets, n_ranks,
         engine.ctx, C.byref(spec), n, ids.ctypes.data, it.ctypes.data,
         int(n_groups), int(n_buckets), int(n_ranks), partials.data_ptr(),
         emit.data_ptr(), rs, _stream(stream)))
+
+
+class DeviceHist:
+    """otsdb_hist_columns for the device entries: the schema as host float32
+    arrays, the [N][K + 2] count matrix as an int64 torch tensor in HBM
+    (None for otsdb_hist_finalize_device, which reads the schema alone)."""
+
+    def __init__(self, lower, upper, counts=None):
+        self.lower = np.ascontiguousarray(lower, dtype=np.float32)
+        self.upper = np.ascontiguousarray(upper, dtype=np.float32)
+        self.counts = counts
+
+    @property
+    def n_bins(self):
+        return len(self.lower)
+
+    def as_abi(self):
+        return abi.HistColumns(self.n_bins, self.lower.ctypes.data,
+                               self.upper.ctypes.data,
+                               None if self.counts is None
+                               else self.counts.data_ptr())
+
+
+class DeviceHistResult:
+    """otsdb_hist_result in HBM: offsets [G + 1], ts [cap], pct [P][cap],
+    counts [cap][K + 2] (want_counts)."""
+
+    def __init__(self, torch, G, cap, n_bins, n_pct, want_counts, device):
+        cap = max(int(cap), 1)
+        self.cap = cap
+        self.offsets = torch.zeros(G + 1, dtype=torch.int64, device=device)
+        self.ts = torch.zeros(cap, dtype=torch.int64, device=device)
+        self.pct = torch.zeros((max(n_pct, 1), cap), dtype=torch.float64,
+                               device=device)
+        self.counts = (torch.zeros((cap, n_bins + 2), dtype=torch.int64,
+                                   device=device) if want_counts else None)
+        self.n_pct = n_pct
+
+    def as_abi(self):
+        return abi.HistResult(self.cap, self.offsets.data_ptr(),
+                              self.ts.data_ptr(),
+                              self.pct.data_ptr() if self.n_pct else None,
+                              None if self.counts is None
+                              else self.counts.data_ptr())
+
+
+def _pct_arg(percentiles):
+    from .histogram import percentile_spec
+    p = percentile_spec(percentiles)
+    return p, (p.ctypes.data if len(p) else None), len(p)
+
+
+def run_hist_device(engine, spec, dbatch, dhist, percentiles, dresult,
+                    stream=None):
+    """Device-resident histogram query (Engine.run_hist's semantics): the
+    result lands in `dresult`, a DeviceHistResult."""
+    p, pp, n = _pct_arg(percentiles)
+    b, h, r = dbatch.as_abi(), dhist.as_abi(), dresult.as_abi()
+    engine._check(engine.lib.otsdb_hist_run_device(
+        engine.ctx, C.byref(spec), C.byref(b), C.byref(h), pp, n, C.byref(r),
+        _stream(stream)))
+
+
+def hist_partials_device(engine, spec, dbatch, dhist, dense, emit,
+                         stream=None):
+    """otsdb_hist_partials_device: this rank's dense sums into `dense` (int64
+    [G, n_buckets, K + 2]) and `emit` (uint8 [G, n_buckets]); the ranks'
+    arrays add up (SUM / MAX) to the single run's."""
+    b, h = dbatch.as_abi(), dhist.as_abi()
+    engine._check(engine.lib.otsdb_hist_partials_device(
+        engine.ctx, C.byref(spec), C.byref(b), C.byref(h), dense.data_ptr(),
+        emit.data_ptr(), _stream(stream)))
+
+
+def hist_finalize_device(engine, spec, dhist, n_groups, n_buckets, dense,
+                         emit, percentiles, dresult, stream=None):
+    """otsdb_hist_finalize_device: percentiles and the compacted result from
+    the (summed) dense arrays."""
+    p, pp, n = _pct_arg(percentiles)
+    h, r = dhist.as_abi(), dresult.as_abi()
+    engine._check(engine.lib.otsdb_hist_finalize_device(
+        engine.ctx, C.byref(spec), C.byref(h), int(n_groups), int(n_buckets),
+        dense.data_ptr(), emit.data_ptr(), pp, n, C.byref(r),
+        _stream(stream)))
