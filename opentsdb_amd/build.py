@@ -3,12 +3,26 @@
 hipcc cross-compiles without a GPU, so this runs in the CPU container; the
 resulting .so travels to the GPU box with the repository snapshot.
 
-The device code is split over translation units compiled in parallel: the
-engine (host code, the non-template kernels — storage rows, rollup rows and
-the histogram query's among them — and the aggregator-templated ones), two units per downsampling monoid (csrc/ds_tu.hip with
--DOTSDB_DS_MONOID=n: the downsample / ordered-fold kernels of that monoid,
-and with -DOTSDB_DS_PART=1 the cells fold of that monoid) and csrc/rollup.hip
-(the prep and ring kernels of the two rollup states, nothing else).
+The library links 28 translation units compiled in parallel (UNIT_FILES
+below names each kind's source and every csrc file it includes; a unit is
+rebuilt when one of those, or include/otsdb_agg.h, is newer than its object):
+
+- three engine units with the host code and the C-ABI: csrc/engine.hip (the
+  context, planning, the pipeline, multi / panel / cells / selection queries,
+  the non-template kernels of kernels.hip and the aggregator-templated ones),
+  csrc/engine_rows.hip (storage rows and rollup rows: rows.hip,
+  rollup_rows.hip) and csrc/engine_hist.hip (histogram queries: hist.hip);
+  csrc/engine_int.h is what they share;
+- two units per downsampling monoid (csrc/ds_tu.hip with -DOTSDB_DS_MONOID=n:
+  the downsample / ordered-fold kernels of that monoid, and with
+  -DOTSDB_DS_PART=1 the cells fold of that monoid);
+- csrc/rollup.hip (the prep and ring kernels of the two rollup states).
+
+Build times on one 8-core machine, each one run.  Clean (force=True): 320 s,
+taken right after the preceding commit's 325 s (that commit, with engine.hip
+as the one engine unit, took 293 - 325 s over three runs as the machine
+drifted).  After touching one file: engine_hist.hip 3 s, engine_rows.hip
+26 s, engine.hip 40 s, against 68 s for the one engine.hip before.
 """
 import glob
 import os
@@ -28,6 +42,28 @@ ARCH = os.environ.get("OTSDB_OFFLOAD_ARCH", "gfx950")
 N_DS_MONOIDS = 12  # dispatch.h with_monoid: distinct reduction state types
 HIPCC = "/opt/rocm/bin/hipcc"
 
+# Every kind of unit: its source, then every csrc file that source includes,
+# directly or through another (tests/test_build_units_cpu.py holds the rows
+# to the #include lines).  A unit is rebuilt when one of its own files, or
+# include/otsdb_agg.h, is newer than its object.
+_SHARED = ("kernels.hip", "kernels.h", "monoids.h", "rollup_monoids.h",
+           "launch.h", "dispatch.h")
+_DS = ("ds_tu.hip", "decode.hip", "fold.hip", "foldmulti.hip",
+       "menv.h") + _SHARED
+UNIT_FILES = {
+    "engine": ("engine.hip", "engine_int.h", "compact.hip", "select.hip",
+               "decode.hip", "raw.hip", "calendar.hip", "multi.hip",
+               "panel.hip", "foldplan.h", "menv.h") + _SHARED,
+    "engine_rows": ("engine_rows.hip", "engine_int.h", "decode.hip",
+                    "rows.hip", "rollup_rows.hip") + _SHARED,
+    "engine_hist": ("engine_hist.hip", "engine_int.h", "compact.hip",
+                    "hist.hip", "histplan.h") + _SHARED,
+    "rollup": ("rollup.hip",) + _SHARED,
+    "ds": _DS,                          # ds_tu.hip, -DOTSDB_DS_PART=0
+    "cells": _DS + ("cellfold.hip",),   # ds_tu.hip, -DOTSDB_DS_PART=1
+}
+ENGINE_UNITS = ("engine", "engine_rows", "engine_hist")
+
 FLAGS = [
     "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC",
     # Java rounds every multiply and add separately: no FMA contraction
@@ -45,18 +81,19 @@ def up_to_date(out=OUT):
 
 
 def _units(out_dir, defines):
+    """(source, flags, object, kind) of every unit: the engine units first,
+    then the longest (part 1, the cells fold: cellfold.hip)."""
     d = ["-D" + x for x in defines]
-    units = [(os.path.join(CSRC, "engine.hip"), d,
-              os.path.join(out_dir, "engine.o")),
-             (os.path.join(CSRC, "rollup.hip"), d,
-              os.path.join(out_dir, "rollup.o"))]
-    # part 1 (the cells fold, cellfold.hip) first: its units are the longest
-    for part in (1, 0):
+    units = [(os.path.join(CSRC, UNIT_FILES[k][0]), d,
+              os.path.join(out_dir, k + ".o"), k)
+             for k in ENGINE_UNITS + ("rollup",)]
+    for part, kind in ((1, "cells"), (0, "ds")):
         for m in range(N_DS_MONOIDS):
             units.append((os.path.join(CSRC, "ds_tu.hip"),
                           d + ["-DOTSDB_DS_MONOID=%d" % m,
                                "-DOTSDB_DS_PART=%d" % part],
-                          os.path.join(out_dir, "ds_%d_%d.o" % (part, m))))
+                          os.path.join(out_dir, "ds_%d_%d.o" % (part, m)),
+                          kind))
     return units
 
 
@@ -73,7 +110,7 @@ def build(force=False, verbose=False, jobs=None, defines=(), out=None):
     jobs = jobs or min(8, os.cpu_count() or 1)
 
     def compile_unit(u):
-        src, extra, obj = u
+        src, extra, obj, _ = u
         cmd = [HIPCC] + FLAGS + extra + ["-c", "-o", obj + ".tmp", src]
         if verbose:
             print(" ".join(cmd), flush=True)
@@ -88,29 +125,21 @@ def build(force=False, verbose=False, jobs=None, defines=(), out=None):
         return obj
 
     units = _units(out_dir, defines)
-    # incremental: a unit is rebuilt when a source it may include is newer
-    # than its object (only part-1 units include cellfold.hip)
-    # sources only engine.hip includes (ds_tu.hip's include graph:
-    # kernels.hip, decode.hip, fold.hip, cellfold.hip and the headers)
-    engine_only = ("engine.hip", "select.hip", "raw.hip", "rows.hip",
-                   "rollup_rows.hip", "calendar.hip", "compact.hip",
-                   "multi.hip", "panel.hip", "hist.hip", "histplan.h",
-                   "foldplan.h")
 
     def stale(u):
-        src, extra, obj = u
+        obj, kind = u[2], u[3]
         if force or not os.path.exists(obj):
             return True
         t = os.path.getmtime(obj)
-        part1 = "-DOTSDB_DS_PART=1" in extra
-        ds = src.endswith(("ds_tu.hip", "rollup.hip"))
-        return any(os.path.getmtime(d) > t for d in DEPS
-                   if (part1 or not d.endswith("cellfold.hip")) and
-                   not (ds and os.path.basename(d) in engine_only) and
-                   (src.endswith("rollup.hip") or
-                    not d.endswith("rollup.hip")))
+        deps = [os.path.join(CSRC, f) for f in UNIT_FILES[kind]] + [DEPS[-1]]
+        return any(os.path.getmtime(d) > t for d in deps)
 
-    todo = [u for u in units if stale(u)]
+    # longest first (a cells unit takes ~2 min of one core, a ds unit ~1 min,
+    # engine.hip 40 s, engine_rows.hip 30 s, the rest seconds): the short ones
+    # fill the pool's tail
+    order = ("cells", "engine", "ds", "engine_rows", "rollup", "engine_hist")
+    todo = sorted((u for u in units if stale(u)),
+                  key=lambda u: order.index(u[3]))
     with ThreadPoolExecutor(jobs) as ex:
         list(ex.map(compile_unit, todo))
     objs = [u[2] for u in units]

@@ -1,7 +1,9 @@
 // compact.hip — the last stage of a query: dense (group, bucket) results ->
 // the per-group (timestamp, value) arrays of otsdb_result (offsets[G+1]),
 // plus the call's {error word, total points} for finish's single read.
-// Included by engine.hip only (the pipeline's other kernels never call it).
+// Its kernels are compiled in engine.hip only; engine_hist.hip includes it
+// under OTSDB_DS_TU for compact_count (the pipeline's other kernels never
+// call it).
 #pragma once
 // (included after kernels.hip: Params, bucket_ts, LANE)
 
@@ -93,6 +95,7 @@ DEV void zero_bytes(uint8_t* __restrict__ r, int64_t a, int64_t e, int64_t cap,
   for (uint8_t* x = qe + lane; x < pe; x += 64) *x = 0;
 }
 
+#ifndef OTSDB_DS_TU
 __global__ __launch_bounds__(256) void k_compact_count(
     Params P, int64_t G, const uint8_t* __restrict__ out_emit,
     int64_t* __restrict__ counts, unsigned long long* __restrict__ ticket,
@@ -288,5 +291,7 @@ __global__ __launch_bounds__(256) void k_compact1(
     pos += __popcll(m);
   }
 }
+
+#endif  // OTSDB_DS_TU
 
 }  // namespace otsdb

@@ -1,7 +1,7 @@
 // ds_tu.hip — the kernels templated on one downsampling monoid, compiled once
 // per monoid with -DOTSDB_DS_MONOID=<n> (opentsdb_amd/build.py runs the
 // thirteen compilations in parallel; the engine links them).  Non-template
-// kernels are compiled only in engine.hip (OTSDB_DS_TU hides them here).
+// kernels are compiled only in the engine units (OTSDB_DS_TU hides them here).
 #define OTSDB_DS_TU 1
 // fused cells kernel shape (tuning builds override)
 #ifndef OTSDB_CELLS_K

@@ -5,6 +5,12 @@
 // stream and maps the device error word back onto the reference's
 // exceptions.  No CPU fallback exists: every data point is produced on the
 // GPU.
+//
+// The storage-row and histogram families live in units of their own
+// (engine_rows.hip, engine_hist.hip); engine_int.h holds what the three
+// share, and every shared function is defined here: the plumbing first, then
+// this unit's own code, then the query implementations the others call, then
+// the C-ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,20 +35,22 @@
 #include "select.hip"
 #include "decode.hip"
 #include "raw.hip"
-#include "rows.hip"
-#include "rollup_rows.hip"
 #include "calendar.hip"
 #include "multi.hip"
 #include "panel.hip"
-#include "hist.hip"
 #include "launch.h"
 #include "foldplan.h"
+#include "engine_int.h"
 
 using namespace otsdb;
+using namespace otsdb::eng;
 
-namespace {
+// ------------------------------------------- shared plumbing (engine_int.h)
 
-thread_local std::string g_last_error;
+namespace otsdb {
+namespace eng {
+
+static thread_local std::string g_last_error;  // otsdb_last_error()
 
 otsdb_status fail(otsdb_status st, const char* fmt, ...) {
   char buf[512];
@@ -53,19 +61,6 @@ otsdb_status fail(otsdb_status st, const char* fmt, ...) {
   g_last_error = buf;
   return st;
 }
-
-#define HIP_TRY(x)                                                        \
-  do {                                                                    \
-    hipError_t e_ = (x);                                                  \
-    if (e_ != hipSuccess)                                                 \
-      return fail(OTSDB_E_DEVICE, "%s: %s", #x, hipGetErrorString(e_));   \
-  } while (0)
-
-struct AggInfo {
-  const char* key;   // Aggregators.get() name
-  const char* name;  // toString()
-  int interp;
-};
 
 const AggInfo kAggs[OTSDB_AGG_COUNT_IDS] = {
     {"sum", "sum", 0},          {"pfsum", "pfsum", 4},
@@ -88,288 +83,18 @@ const AggInfo kAggs[OTSDB_AGG_COUNT_IDS] = {
     {"ep50r7", "ep50r7", 0},
 };
 
-bool is_selection(int agg) {
-  return agg == OTSDB_AGG_MEDIAN || agg >= OTSDB_AGG_P999;
-}
-
-double pct_of(int agg) {  // PercentileAgg(percentile).evaluate(): p / 100d
-  static const double P[6] = {99.9, 99.0, 95.0, 90.0, 75.0, 50.0};
-  return P[(agg - OTSDB_AGG_P999) % 6] / 100.0;
-}
-
-inline int64_t jmod(int64_t a, int64_t b) { return a % b; }
-inline int64_t align_down(int64_t t, int64_t iv) { return t - jmod(t, iv); }
-
-constexpr int64_t kChunk = 256;  // series per cross-series chunk
-
-// k_keys_transpose's grid: KT_M members x OTSDB_KT_SLICES bucket slices
-dim3 kt_grid(int64_t M, int64_t NB) {
-  const int64_t ntb = (NB + 63) / 64;
-  const int64_t sl = ntb < OTSDB_KT_SLICES ? (ntb > 0 ? ntb : 1) : OTSDB_KT_SLICES;
-  return dim3((unsigned)((M + KT_M - 1) / KT_M), (unsigned)sl);
-}
-
-// (the ordered fold's tile sizes and window rule: foldplan.h)
-// An ordered (dev) group past one fold tile (kOrderedFoldChunk) takes the row
-// path's k_group with one chain of up to kOrderedChunk members (one thread
-// walks them in SpanCmp order; ~100 ns a member: tools/chain_probe.hip, 69 ns
-// with no memory at all, so a 500k-member chain — C4 — would cost ~50 ms).
-// Larger groups merge 256-member chunk partials in order (Chan); across ranks
-// the chain is handed on (otsdb_agg_partials_chained_device).
-constexpr int64_t kOrderedChunk = 65536;
-constexpr int64_t kOrderedChunkMerged = 16384;
-// the row path's bucket rows an ordered (dev) query may take for groups past
-// one fold tile: fixed, so the path (and the reduction order) never depends
-// on the device's free memory at call time
-constexpr double kOrderedRowBudget = 48.0e9;
-// up to this many (series, window boundary) pairs k_prep and k_fold_prep run
-// as one launch (each pair's thread finds its series' bounds again: cheap
-// next to a launch on small queries, not on the named query's 400,000)
-#ifndef OTSDB_PREP_FOLD_MAX
-#define OTSDB_PREP_FOLD_MAX 65536
-#endif
-// (the environment's OTSDB_PREP_FOLD_MAX overrides it: the tests run both
-// forms on one process)
-int64_t prep_fold_max() {
-  const char* e = getenv("OTSDB_PREP_FOLD_MAX");
-  return e ? atoll(e) : (int64_t)OTSDB_PREP_FOLD_MAX;
-}
-
-// the storage rows cannot be taken verbatim (run_raw_verbatim): flagged on
-// the context, never returned through the C-ABI
-otsdb_status spec_miss(otsdb_ctx* c);
-
-struct Carve {
-  char* base;
-  size_t off = 0;
-  template <class T>
-  T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = reinterpret_cast<T*>(base + off);
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
-// device buffers of one query's pipeline, carved from the context workspace
-struct Work {
-  SeriesMeta SM;
-  Rows R;
-  Packed* partial;
-  uint8_t* tile_emit;
-  double* out_val;
-  uint8_t* out_emit;
-  int64_t* counts;
-  uint64_t* keys = nullptr;
-  uint64_t* key_mm = nullptr;  // per (bucket, 64-member tile) min / max key
-  uint32_t* key_cnt = nullptr;  // per (bucket, tile) non-NaN keys (fill mode)
-  uint32_t* lg_kept = nullptr;  // per large group: holds a kept series
-  SelState* sel = nullptr;
-  XSel* xsel = nullptr;        // cross-rank selection (mode 2)
-  Packed* comb = nullptr;      // two-level combine: first-level slices
-  uint8_t* comb_emit = nullptr;
-  uint8_t* redo = nullptr;     // fused-rate series handed back (Params.redo)
-  bool sel_fused = false;      // fill-mode selection: keys + counts by the transpose
-};
-
-// The blocks run_pipeline's and multi_build's carves have in common, each in
-// the one order of takes both rely on.
-void carve_series(Carve& cv, Work& W, int64_t S) {
-  W.SM.lo = cv.take<int64_t>(S);
-  W.SM.hi = cv.take<int64_t>(S);
-  W.SM.of_ts = cv.take<int64_t>(S);
-  W.SM.of_val = cv.take<double>(S);
-  W.SM.of_rate = cv.take<double>(S);
-  W.SM.kf = cv.take<int32_t>(S);
-  W.SM.kl = cv.take<int32_t>(S);
-  W.SM.keep = cv.take<uint8_t>(S);
-  W.SM.of_has = cv.take<uint8_t>(S);
-  W.redo = cv.take<uint8_t>(S);
-}
-
-// members: all groups' (goff.back()); LG: the large groups; xsel: mode 2
-void carve_selection(Carve& cv, Work& W, int64_t members, int64_t LG,
-                     int64_t NB, bool xsel) {
-  const size_t kt = (size_t)((members + KT_M - 1) / KT_M) * NB;
-  W.keys = cv.take<uint64_t>((size_t)members * NB);
-  W.key_mm = cv.take<uint64_t>(kt * 2);
-  W.key_cnt = cv.take<uint32_t>(kt);
-  W.lg_kept = cv.take<uint32_t>((size_t)LG + 1);
-  W.sel = cv.take<SelState>((size_t)LG * NB);
-  if (xsel) W.xsel = cv.take<XSel>((size_t)LG * NB);
-}
-
-}  // namespace
-
-struct otsdb_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  void* ws = nullptr;
-  size_t ws_cap = 0;
-  void* stage = nullptr;
-  size_t stage_cap = 0;
-  int* d_err = nullptr;                 // device error word
-  unsigned long long* d_mm = nullptr;   // k_bounds min/max
-  int64_t* h_small = nullptr;           // pinned readback
-  // {error word, total points} of the last compaction, written by the
-  // kernel straight into host memory (coherent, mapped): no read-back copy
-  int64_t* h_done = nullptr;
-  int64_t* d_done = nullptr;            // its device address
-  // tile plan cache (keyed by the group offsets)
-  std::vector<int64_t> goff_cache;
-  int64_t* d_tiles = nullptr;
-  size_t d_tiles_cap = 0;
-  int64_t n_tiles = 0, n_multi = 0, n_large = 0, n_large_chunks = 0;
-  int64_t max_chunks = 0;  // most chunks in one group
-  bool tiles_sel_all = false;
-  int64_t tiles_chunk = 0;
-  int64_t tiles_whole = 0;
-  bool verbatim = false;  // run_raw_verbatim: the cells query's rows as stored
-  // a rollup call (otsdb_agg_run_rollup*, RollupScope): the rollup state its
-  // rows are built with and the points' value_count column (device)
-  RollupKind rollup = ROLLUP_NONE;
-  const int64_t* rollup_cnt = nullptr;
-  // the cells fold's uniform kernel met a qualifier that is not its series'
-  // (ERR_CELLS_NONUNI): this call's next attempt takes the general kernel
-  bool cells_no_uni = false;
-  // otsdb_ctx_counters: cells folds launched uniform / general, uniform
-  // folds that missed (ERR_CELLS_NONUNI, re-run with the general kernel)
-  int64_t n_cells_uniform = 0, n_cells_general = 0, n_cells_uni_miss = 0;
-  bool spec_miss = false;  // ... and they cannot be: the caller compacts
-  bool result_short = false;  // the last E_CAPACITY was the result's (finish)
-  std::mutex mu;  // one query at a time per context
-  // stage timing (otsdb_prof_*)
-  bool prof = false;
-  std::vector<hipEvent_t> ev_pool;
-  std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev_pending;
-  size_t ev_used = 0;
-  double prof_ms[12] = {0};
-  int64_t prof_n[12] = {0};
-  void* cells_ws = nullptr;  // cells query: series row / point offsets
-  size_t cells_ws_cap = 0;
-  void* cells_col = nullptr;  // cells query fallback: decoded columns
-  size_t cells_col_cap = 0;
-  void* cal = nullptr;  // calendar bucket edges of the current query
-  size_t cal_cap = 0;
-  void* acal_fill = nullptr;  // stage A' (calendar fill): compacted batch
-  size_t acal_fill_cap = 0;
-  void* acal = nullptr;  // per-series calendar: chains, anchors, series'
-  size_t acal_cap = 0;   // chain positions and bucket-start timestamps
-  void* dec_ws = nullptr;  // decode workspace
-  size_t dec_ws_cap = 0;
-  int dec_generic = 0;  // the last decode count pass: bit 0 / 1, k_decode_generic counts / writes
-  void* ws2 = nullptr;     // raw group-by: candidates, sort, selection slab
-  size_t ws2_cap = 0;
-  void* rows_ws = nullptr;  // storage-row compaction / span assembly: per-row
-  size_t rows_ws_cap = 0;   // and per-series plan arrays
-  void* rows_scr = nullptr;  // GENERAL-row cell records + staging / replay arenas
-  size_t rows_scr_cap = 0;
-  void* rows_large = nullptr;  // LARGE rows: ranked columns, keys, sort temp
-  size_t rows_large_cap = 0;
-  void* raw_cells[2] = {nullptr, nullptr};  // raw-row query: compacted rows,
-  size_t raw_cells_cap[2] = {0, 0};          // then the assembled spans
-  void* raw_stage = nullptr;  // otsdb_agg_run_raw: host rows staged in HBM
-  size_t raw_stage_cap = 0;
-  // single-pass compaction (k_compact1): per-group look-back granules and
-  // the call's epoch; {error word, total} read back in one copy
-  void* cmp_flags = nullptr;
-  size_t cmp_flags_cap = 0;
-  uint32_t cmp_epoch = 0;
-  // the device error word is known to be zero (the last call ended with the
-  // one-pass compaction, which zeroes it): the next pipeline skips its
-  // memset.  clean_entry: that mark as the current call found it (CtxLock)
-  bool err_clean = false;
-  bool clean_entry = false;
-  bool small_ready = false;  // k_compact1 wrote {error word, total}
-  // multi-aggregator calls (otsdb_agg_run_multi*): one device error word per
-  // output, and per output the compaction's {error word, total, look-back
-  // mark, -} in mapped host memory (the call synchronises once, at its end)
-  int* d_merr = nullptr;
-  int64_t* h_mdone = nullptr;
-  int64_t* d_mdone = nullptr;
-  int multi_failed = -1;  // the output whose status the last multi call returned
-  int64_t multi_total[OTSDB_MULTI_MAX] = {0};  // points of each output
-  // otsdb_ctx_counters [5..8], of the last multi call: downsample passes over
-  // the point stream, group-stage passes over a row matrix, key transposes,
-  // transform passes
-  int64_t n_multi_ds = 0, n_multi_group = 0, n_multi_kt = 0, n_multi_tf = 0;
-  // otsdb_ctx_counters [12], of the last multi call: k_fold_multi launches
-  // (OTSDB_SPEC_MULTI_FOLD on an eligible request: 1, else 0)
-  int64_t n_multi_fold = 0;
-  // otsdb_ctx_counters [10..11], of the last panel call: passes over the
-  // point stream, row matrices built
-  int64_t n_panel_passes = 0, n_panel_mats = 0;
-  // otsdb_ctx_counters [13..14], of the last otsdb_hist_* call: k_hist_fold
-  // launches, percentile passes over the dense sums
-  int64_t n_hist_fold = 0, n_hist_pct = 0;
-  // cross-rank selection session (otsdb_sel_*): lives in `ws` between calls
-  struct {
-    bool active = false;
-    Params P;
-    otsdb_query_spec spec;
-    Work W;
-    int64_t G = 0, NB = 0, M = 0;
-    int median = 0;
-    int32_t next_pass = 0;   // the pass otsdb_sel_hist_device expects
-    bool more = false;       // the last planned pass has work
-    bool pool_built = false;  // pass 1 compacted the candidates
-    bool need_pick = false;
-    // diagnostics (otsdb_ctx_counters): passes over the local key matrix
-    // and histogram passes of the last session
-    int64_t key_reads = 0, passes = 0;
-    int64_t sessions = 0;  // prepared since the context was created ([9])
-    void* pool = nullptr;    // candidates: keys [cap] | segments [cap]
-    size_t pool_bytes = 0;
-    int64_t pool_cap = 0;
-    // per segment: pool bounds [GB+1] | region offsets [GB+1] | fill [GB] |
-    // the offsets' scan storage
-    void* segmem = nullptr;
-    size_t segmem_bytes = 0, scan_tmp = 0;
-  } sel;
-};
-
-namespace {
-
-otsdb_status ensure(void** p, size_t* cap, size_t need) {
-  if (need <= *cap) return OTSDB_OK;
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
+otsdb_status DevBuf::ensure(size_t need) {
+  if (need <= cap) return OTSDB_OK;
+  if (p) hipFree(p);
+  p = nullptr;
+  cap = 0;
   size_t n = std::max(need, (size_t)1 << 20);
-  hipError_t e = hipMalloc(p, n);
+  hipError_t e = hipMalloc(&p, n);
   if (e != hipSuccess)
     return fail(OTSDB_E_DEVICE, "hipMalloc(%zu): %s", n, hipGetErrorString(e));
-  *cap = n;
+  cap = n;
   return OTSDB_OK;
 }
-
-// One call at a time per context.  Also takes the "error word known zero"
-// mark for this call (clean_entry) and clears it: only the one-pass
-// compaction's read-back (finish) sets it again, after k_compact1 zeroed
-// the word — any other call may leave bits in it.
-// A cross-rank selection session lives in the workspace the other entries
-// overwrite: every call ends it, except the session's own entries and the
-// diagnostics (keep_session), so that a late otsdb_sel_* call reports
-// E_ILLEGAL_STATE instead of reading another query's bytes.
-struct CtxLock {
-  std::lock_guard<std::mutex> lk;
-  explicit CtxLock(otsdb_ctx* c, bool keep_session = false) : lk(c->mu) {
-    c->clean_entry = c->err_clean;
-    c->err_clean = false;
-    if (!keep_session) c->sel.active = false;
-  }
-};
-
-// Binds a caller's stream to the context for one call and restores the
-// context's own stream on every exit path (early HIP_TRY returns included).
-struct StreamBinding {
-  otsdb_ctx* c;
-  hipStream_t saved;
-  StreamBinding(otsdb_ctx* c_, void* hip_stream) : c(c_), saved(c_->stream) {
-    if (hip_stream) c->stream = (hipStream_t)hip_stream;
-  }
-  ~StreamBinding() { c->stream = saved; }
-};
 
 // the context's error word after everything queued on its stream
 otsdb_status read_err(otsdb_ctx* c, int* e) {
@@ -380,37 +105,10 @@ otsdb_status read_err(otsdb_ctx* c, int* e) {
   return OTSDB_OK;
 }
 
-// ERR_RATE_TS as the entries that leave partials report it
-otsdb_status rate_ts_error() {
-  return fail(OTSDB_E_ILLEGAL_STATE,
-              "Next timestamp is supposed to be strictly greater");
-}
-
 BatchDev batch_dev(const otsdb_batch* b) {
   return BatchDev{b->n_series, b->offsets, b->ts_ms, b->val, b->is_float,
                   b->series_float};
 }
-
-// ts_ms / val off the 16-byte alignment of the streaming loads
-bool misaligned(const otsdb_batch* b) {
-  return ((((uintptr_t)b->ts_ms) | ((uintptr_t)b->val)) & 15) != 0;
-}
-
-// what a multi-aggregator call counts: downsample and group passes (0, 0:
-// the reset), no key transpose or class transform yet
-void multi_counters(otsdb_ctx* c, int64_t ds, int64_t group) {
-  c->n_multi_ds = ds;
-  c->n_multi_group = group;
-  c->n_multi_kt = c->n_multi_tf = 0;
-  c->n_multi_fold = 0;
-}
-
-// --------------------------------------------------------------- planning
-struct Plan {
-  Params P;
-  int64_t S, G, M, N;
-  bool sel;  // percentile/median across series
-};
 
 otsdb_status check_spec(const otsdb_query_spec* s) {
   if (s->agg_id < 0 || s->agg_id >= OTSDB_AGG_COUNT_IDS)
@@ -477,6 +175,198 @@ otsdb_status check_spec(const otsdb_query_spec* s) {
   return OTSDB_OK;
 }
 
+// a host entry's result too small: the caller still gets the offsets the
+// whole result needs (offsets[G] = its point count), then the status
+otsdb_status copy_offsets_back(otsdb_ctx* c, otsdb_result* out,
+                               const int64_t* d_offsets, int64_t G,
+                               otsdb_status rc) {
+  HIP_TRY(hipMemcpyAsync(out->offsets, d_offsets, 8 * (G + 1),
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return rc;
+}
+
+otsdb_status read_goff(otsdb_ctx* c, const otsdb_batch* b, bool device,
+                       std::vector<int64_t>& goff) {
+  goff.resize(b->n_groups + 1);
+  if (b->n_groups < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "n_groups < 0");
+  if (!b->group_offsets) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "no groups");
+  if (device && b->group_offsets_host) {
+    // the caller's host copy of the same offsets: no read-back, no sync
+    // (the caller keeps it equal to the device array: include/otsdb_agg.h)
+    memcpy(goff.data(), b->group_offsets_host, sizeof(int64_t) * goff.size());
+#ifdef OTSDB_DEBUG_SYNC
+    {  // debug builds: the host copy's total against the device's
+      int64_t last = 0;
+      HIP_TRY(hipMemcpyAsync(&last, b->group_offsets + b->n_groups,
+                             sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      if (last != goff.back())
+        return fail(OTSDB_E_ILLEGAL_ARGUMENT,
+                    "group_offsets_host[G] %lld != device %lld",
+                    (long long)goff.back(), (long long)last);
+    }
+#endif
+  } else if (device) {
+    HIP_TRY(hipMemcpyAsync(goff.data(), b->group_offsets,
+                           sizeof(int64_t) * goff.size(),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  } else {
+    memcpy(goff.data(), b->group_offsets, sizeof(int64_t) * goff.size());
+  }
+  for (size_t i = 1; i < goff.size(); ++i)
+    if (goff[i] < goff[i - 1])
+      return fail(OTSDB_E_ILLEGAL_ARGUMENT, "group_offsets not monotonic");
+  return OTSDB_OK;
+}
+
+// one exclusive scan of n + 1 int64 (in[n] must be 0), on st
+otsdb_status scan_excl(void* tmp, size_t tmp_bytes, const int64_t* in,
+                       int64_t* out, int64_t n, hipStream_t st) {
+  size_t t = tmp_bytes;
+  HIP_TRY(rocprim::exclusive_scan(tmp, t, in, out, (int64_t)0, (size_t)(n + 1),
+                                  rocprim::plus<int64_t>(), st));
+  return OTSDB_OK;
+}
+
+size_t scan_tmp_bytes(int64_t n, hipStream_t st) {
+  size_t b = 0;
+  rocprim::exclusive_scan(nullptr, b, (const int64_t*)nullptr, (int64_t*)nullptr,
+                          (int64_t)0, (size_t)(n + 1), rocprim::plus<int64_t>(),
+                          st);
+  return (b + 255) & ~(size_t)255;
+}
+
+// the storage rows cannot be taken verbatim (run_raw_verbatim): flagged on
+// the context, never returned through the C-ABI
+otsdb_status spec_miss(otsdb_ctx* c) {
+  c->spec_miss = true;
+  return OTSDB_E_UNSUPPORTED;
+}
+
+// (kernels of this unit for the other units: engine_int.h)
+void launch_scan(int64_t n, const int64_t* counts, int64_t* offsets,
+                 hipStream_t st) {
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, n, counts, offsets);
+}
+
+void launch_series_rows(int64_t R, int64_t S, const int64_t* row_series,
+                        int64_t* series_row, hipStream_t st) {
+  hipLaunchKernelGGL(k_series_rows, dim3(blocks_for(R + 1, 256)), dim3(256), 0,
+                     st, R, S, row_series, series_row);
+}
+
+void launch_series_offsets(int64_t R, int64_t S, const int64_t* row_series,
+                           const int64_t* row_out, int64_t* offsets,
+                           hipStream_t st) {
+  hipLaunchKernelGGL(k_series_offsets, dim3(blocks_for(R + 1, 256)), dim3(256),
+                     0, st, R, S, row_series, row_out, offsets);
+}
+
+}  // namespace eng
+}  // namespace otsdb
+
+namespace {
+
+bool is_selection(int agg) {
+  return agg == OTSDB_AGG_MEDIAN || agg >= OTSDB_AGG_P999;
+}
+
+double pct_of(int agg) {  // PercentileAgg(percentile).evaluate(): p / 100d
+  static const double P[6] = {99.9, 99.0, 95.0, 90.0, 75.0, 50.0};
+  return P[(agg - OTSDB_AGG_P999) % 6] / 100.0;
+}
+
+constexpr int64_t kChunk = 256;  // series per cross-series chunk
+
+// k_keys_transpose's grid: KT_M members x OTSDB_KT_SLICES bucket slices
+dim3 kt_grid(int64_t M, int64_t NB) {
+  const int64_t ntb = (NB + 63) / 64;
+  const int64_t sl = ntb < OTSDB_KT_SLICES ? (ntb > 0 ? ntb : 1) : OTSDB_KT_SLICES;
+  return dim3((unsigned)((M + KT_M - 1) / KT_M), (unsigned)sl);
+}
+
+// (the ordered fold's tile sizes and window rule: foldplan.h)
+// An ordered (dev) group past one fold tile (kOrderedFoldChunk) takes the row
+// path's k_group with one chain of up to kOrderedChunk members (one thread
+// walks them in SpanCmp order; ~100 ns a member: tools/chain_probe.hip, 69 ns
+// with no memory at all, so a 500k-member chain — C4 — would cost ~50 ms).
+// Larger groups merge 256-member chunk partials in order (Chan); across ranks
+// the chain is handed on (otsdb_agg_partials_chained_device).
+constexpr int64_t kOrderedChunk = 65536;
+constexpr int64_t kOrderedChunkMerged = 16384;
+// the row path's bucket rows an ordered (dev) query may take for groups past
+// one fold tile: fixed, so the path (and the reduction order) never depends
+// on the device's free memory at call time
+constexpr double kOrderedRowBudget = 48.0e9;
+// up to this many (series, window boundary) pairs k_prep and k_fold_prep run
+// as one launch (each pair's thread finds its series' bounds again: cheap
+// next to a launch on small queries, not on the named query's 400,000)
+#ifndef OTSDB_PREP_FOLD_MAX
+#define OTSDB_PREP_FOLD_MAX 65536
+#endif
+// (the environment's OTSDB_PREP_FOLD_MAX overrides it: the tests run both
+// forms on one process)
+int64_t prep_fold_max() {
+  const char* e = getenv("OTSDB_PREP_FOLD_MAX");
+  return e ? atoll(e) : (int64_t)OTSDB_PREP_FOLD_MAX;
+}
+
+// The blocks run_pipeline's and multi_build's carves have in common, each in
+// the one order of takes both rely on.
+void carve_series(Carve& cv, Work& W, int64_t S) {
+  W.SM.lo = cv.take<int64_t>(S);
+  W.SM.hi = cv.take<int64_t>(S);
+  W.SM.of_ts = cv.take<int64_t>(S);
+  W.SM.of_val = cv.take<double>(S);
+  W.SM.of_rate = cv.take<double>(S);
+  W.SM.kf = cv.take<int32_t>(S);
+  W.SM.kl = cv.take<int32_t>(S);
+  W.SM.keep = cv.take<uint8_t>(S);
+  W.SM.of_has = cv.take<uint8_t>(S);
+  W.redo = cv.take<uint8_t>(S);
+}
+
+// members: all groups' (goff.back()); LG: the large groups; xsel: mode 2
+void carve_selection(Carve& cv, Work& W, int64_t members, int64_t LG,
+                     int64_t NB, bool xsel) {
+  const size_t kt = (size_t)((members + KT_M - 1) / KT_M) * NB;
+  W.keys = cv.take<uint64_t>((size_t)members * NB);
+  W.key_mm = cv.take<uint64_t>(kt * 2);
+  W.key_cnt = cv.take<uint32_t>(kt);
+  W.lg_kept = cv.take<uint32_t>((size_t)LG + 1);
+  W.sel = cv.take<SelState>((size_t)LG * NB);
+  if (xsel) W.xsel = cv.take<XSel>((size_t)LG * NB);
+}
+
+// ERR_RATE_TS as the entries that leave partials report it
+otsdb_status rate_ts_error() {
+  return fail(OTSDB_E_ILLEGAL_STATE,
+              "Next timestamp is supposed to be strictly greater");
+}
+
+// ts_ms / val off the 16-byte alignment of the streaming loads
+bool misaligned(const otsdb_batch* b) {
+  return ((((uintptr_t)b->ts_ms) | ((uintptr_t)b->val)) & 15) != 0;
+}
+
+// what a multi-aggregator call counts: downsample and group passes (0, 0:
+// the reset), no key transpose or class transform yet
+void multi_counters(otsdb_ctx* c, int64_t ds, int64_t group) {
+  c->n_multi_ds = ds;
+  c->n_multi_group = group;
+  c->n_multi_kt = c->n_multi_tf = 0;
+  c->n_multi_fold = 0;
+}
+
+// --------------------------------------------------------------- planning
+struct Plan {
+  Params P;
+  int64_t S, G, M, N;
+  bool sel;  // percentile/median across series
+};
+
 // Calendar grid (otsdb_query_spec.cal_edges): the fixed-interval rules of
 // make_params restated on the edge table — seek to the first edge >= start
 // (ValuesInInterval.seekInterval rounds up, Downsampler.java:431-441), NONE:
@@ -521,11 +411,11 @@ otsdb_status make_cal_params(const otsdb_query_spec* s, Params* P,
   P->cal_n = n - k_seek;
   P->cal = nullptr;
   if (c) {
-    otsdb_status rc = ensure(&c->cal, &c->cal_cap, sizeof(int64_t) * n);
+    otsdb_status rc = c->cal.ensure(sizeof(int64_t) * n);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->cal, e, sizeof(int64_t) * n,
+    HIP_TRY(hipMemcpyAsync(c->cal.p, e, sizeof(int64_t) * n,
                            hipMemcpyHostToDevice, c->stream));
-    P->cal = (const int64_t*)c->cal + k_seek;
+    P->cal = (const int64_t*)c->cal.p + k_seek;
   }
   return OTSDB_OK;
 }
@@ -541,73 +431,6 @@ void agg_params(Params* P, int agg_id, int interp) {
                                             : 7;
 }
 
-// Grid of buckets every series row is laid out on.
-otsdb_status make_params(const otsdb_query_spec* s, Params* P,
-                         otsdb_ctx* c = nullptr) {
-  memset(P, 0, sizeof(*P));
-  P->start_ms = s->start_ms;
-  P->end_ms = s->end_ms;
-  P->run_all = s->run_all;
-  P->fill = s->run_all ? 0 : s->fill;
-  P->rate = s->rate;
-  P->counter = s->counter;
-  P->drop_resets = s->drop_resets;
-  P->counter_max = s->counter_max;
-  P->reset_value = s->reset_value;
-  agg_params(P, s->agg_id, s->interp);
-  P->fill_value = (P->fill == OTSDB_FILL_ZERO) ? 0.0 : NAN;
-  if (!(s->ds_interval_ms > 0 || s->run_all)) return OTSDB_OK;  // raw
-  if (is_selection(s->ds_agg_id)) {
-    P->ds_sel = s->ds_agg_id == OTSDB_AGG_MEDIAN ? 1 : 2;
-    P->ds_pct = s->ds_agg_id >= OTSDB_AGG_P999 ? pct_of(s->ds_agg_id) : 0.0;
-  }
-  P->rate_origin_ts = 0;
-  P->rate_origin_val = 0.0;
-  if (s->run_all) {
-    // Downsampler "all": one point at query_start holding the points of
-    // [query_start, query_end) after seek(start) (Downsampler.java:354-379)
-    P->interval = 1;
-    P->inv_interval = 1.0;
-    P->gbase = s->query_start_ms;
-    P->out_ts0 = s->query_start_ms;
-    P->seek_ts = std::max(s->start_ms, s->query_start_ms);
-    P->stop_ts = s->query_end_ms;
-    P->nb = (s->query_start_ms >= s->start_ms &&
-             s->query_start_ms <= s->end_ms) ? 1 : 0;
-    P->narrow = 1;  // every point is bucket 0
-    return OTSDB_OK;
-  }
-  const int64_t iv = s->ds_interval_ms;
-  P->interval = iv;
-  P->inv_interval = 1.0 / (double)iv;
-  if (s->use_calendar && s->n_cal_anchors > 0)  // callers derive stage B
-    return fail(OTSDB_E_UNSUPPORTED,
-                "per-series calendar grids on this entry point");
-  if (s->use_calendar) return make_cal_params(s, P, c);
-  const int64_t grid0 = align_down(s->start_ms + iv - 1, iv);
-  P->gbase = grid0;
-  P->seek_ts = grid0;
-  if (P->fill) {
-    // FillingDownsampler: every bucket of [align(start), align(end)); the
-    // aggregation iterator skips those before start (FillingDownsampler.java
-    // :136-142, AggregationIterator.java:425-447)
-    const int64_t aend = align_down(s->end_ms, iv);
-    P->nb = aend > grid0 ? (aend - grid0) / iv : 0;
-    P->stop_ts = grid0 + P->nb * iv;
-    const int64_t astart = align_down(s->start_ms, iv);
-    if (astart < grid0) {
-      P->rate_origin_ts = astart;
-      P->rate_origin_val = P->fill_value;
-    }
-  } else {
-    P->nb = s->end_ms >= grid0 ? (s->end_ms - grid0) / iv + 1 : 0;
-    P->stop_ts = grid0 + P->nb * iv;
-  }
-  // points fed to the bucket fold lie in [gbase, stop_ts): 32-bit offsets
-  P->narrow = iv < (int64_t(1) << 31) && P->nb < (int64_t(1) << 32) / iv;
-  return OTSDB_OK;
-}
-
 // Per-series calendar grids (calendar.hip): the union grid U of stage B,
 // each anchor's chain terminator, the window's seek and the stage-B spec.
 struct AnchoredPlan {
@@ -620,11 +443,6 @@ struct AnchoredPlan {
   int64_t t_end = 0;
   otsdb_query_spec derived;
 };
-
-bool anchored(const otsdb_query_spec* s) {
-  return s->use_calendar && !s->run_all && s->n_cal_anchors > 0 &&
-         s->ds_interval_ms > 0;
-}
 
 otsdb_status plan_anchored(const otsdb_query_spec* s, AnchoredPlan* A) {
   const int64_t n = s->n_cal_edges, na = s->n_cal_anchors;
@@ -697,7 +515,7 @@ otsdb_status plan_anchored(const otsdb_query_spec* s, AnchoredPlan* A) {
 otsdb_status build_tiles(otsdb_ctx* c, const std::vector<int64_t>& goff,
                          bool sel_all = false, int64_t chunk = kChunk,
                          int64_t whole_upto = 0) {
-  if (c->d_tiles && goff == c->goff_cache && sel_all == c->tiles_sel_all &&
+  if (c->d_tiles.p && goff == c->goff_cache && sel_all == c->tiles_sel_all &&
       chunk == c->tiles_chunk && whole_upto == c->tiles_whole)
     return OTSDB_OK;
   const int64_t G = (int64_t)goff.size() - 1;
@@ -738,11 +556,7 @@ otsdb_status build_tiles(otsdb_ctx* c, const std::vector<int64_t>& goff,
   //         lg_g lg_off lg_k [LG] | lg_ch0 [LG+1] | single [T]
   const size_t n64 = 3 * T + 3 * MG + 3 * G + 4 * LG + 1;
   const size_t bytes = n64 * 8 + T + 64;
-  void* p = c->d_tiles;
-  size_t cap = c->d_tiles_cap;
-  otsdb_status st = ensure(&p, &cap, bytes);
-  c->d_tiles = (int64_t*)p;
-  c->d_tiles_cap = cap;
+  otsdb_status st = c->d_tiles.ensure(bytes);
   if (st) return st;
   std::vector<int64_t> h;
   h.reserve(n64);
@@ -760,10 +574,10 @@ otsdb_status build_tiles(otsdb_ctx* c, const std::vector<int64_t>& goff,
   h.insert(h.end(), lgk.begin(), lgk.end());
   h.insert(h.end(), lgc.begin(), lgc.end());
   if (!h.empty())
-    HIP_TRY(hipMemcpyAsync(c->d_tiles, h.data(), n64 * 8,
+    HIP_TRY(hipMemcpyAsync(c->d_tiles.p, h.data(), n64 * 8,
                            hipMemcpyHostToDevice, c->stream));
   if (T)
-    HIP_TRY(hipMemcpyAsync((char*)c->d_tiles + n64 * 8, single.data(), T,
+    HIP_TRY(hipMemcpyAsync((char*)c->d_tiles.p + n64 * 8, single.data(), T,
                            hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->goff_cache = goff;
@@ -789,7 +603,7 @@ struct Tiles {
 Tiles tiles_of(otsdb_ctx* c, int64_t G) {
   Tiles t;
   const int64_t T = c->n_tiles, MG = c->n_multi;
-  const int64_t* b = c->d_tiles;
+  const int64_t* b = (const int64_t*)c->d_tiles.p;
   t.tg = b;
   t.tm0 = b + T;
   t.tm1 = b + 2 * T;
@@ -832,40 +646,6 @@ void carve_combine(Carve& cv, Work& W, int64_t n_comb, int64_t NB) {
   W.comb = cv.take<Packed>((size_t)n_comb * kCombineSlices * NB);
   W.comb_emit = cv.take<uint8_t>((size_t)n_comb * kCombineSlices * NB);
 }
-
-// Brackets a pipeline stage with HIP events when profiling is enabled.
-struct StageTimer {
-  otsdb_ctx* c;
-  int stage;
-  hipEvent_t a = nullptr, b = nullptr;
-  hipEvent_t get() {
-    if (c->ev_used == c->ev_pool.size()) {
-      hipEvent_t e;
-      hipEventCreate(&e);
-      c->ev_pool.push_back(e);
-    }
-    return c->ev_pool[c->ev_used++];
-  }
-  StageTimer(otsdb_ctx* c_, int s_) : c(c_), stage(s_) {
-    if (c->prof) {
-      a = get();
-      hipEventRecord(a, c->stream);
-    }
-  }
-  ~StageTimer() {
-    if (c->prof) {
-      b = get();
-      hipEventRecord(b, c->stream);
-      c->ev_pending.push_back({stage, {a, b}});
-    }
-  }
-};
-
-inline unsigned blocks_for(int64_t n, int per) {
-  return (unsigned)((n + per - 1) / per);
-}
-
-
 
 template <class M>
 void launch_combine(otsdb_ctx* c, const Work& W, int64_t NB, int64_t n,
@@ -1388,9 +1168,9 @@ otsdb_status run_pipeline(otsdb_ctx* c, const otsdb_query_spec* spec,
     return cv.off + 256;
   };
   const size_t need = carve(nullptr);
-  rc = ensure(&c->ws, &c->ws_cap, need);
+  rc = c->ws.ensure(need);
   if (rc) return rc;
-  carve((char*)c->ws);
+  carve((char*)c->ws.p);
 
   // the error word (+ the cells fold's "wide" word): zero already when the
   // previous call ended in the one-pass compaction
@@ -1511,14 +1291,12 @@ otsdb_status compact(otsdb_ctx* c, const Params& P, int64_t G,
   // scan, scatter); longer: k_compact_count, k_scan, k_compact_scatter.
   // Either way the call's {error word, total} lands in `small` (mapped host
   // memory) for finish.  Scratch: flags [G] (one pass) or counts [G]
-  void* p = c->cmp_flags;
-  size_t cap = c->cmp_flags_cap;
   const size_t need = (size_t)G * 8 + 256;
-  const bool grow = need > cap;
-  otsdb_status rc = ensure(&p, &cap, need);
-  c->cmp_flags = p;
-  c->cmp_flags_cap = cap;
+  const bool grow = need > c->cmp_flags.cap;
+  otsdb_status rc = c->cmp_flags.ensure(need);
   if (rc) return rc;
+  void* p = c->cmp_flags.p;
+  const size_t cap = c->cmp_flags.cap;
   // epochs 1, 2, ..., 2^24 - 1, then 4, 5, ...: never 0 (fresh granules)
   // and always one ticket slot on from the last call's (k_compact1).  A
   // granule is taken as this call's by its epoch alone, so when the epoch
@@ -1557,7 +1335,36 @@ otsdb_status compact(otsdb_ctx* c, const Params& P, int64_t G,
   return OTSDB_OK;
 }
 
-otsdb_status result_status(int err, int64_t total, int64_t capacity);
+// the status of one result: its device error word, then its capacity
+otsdb_status result_status(int err, int64_t total, int64_t capacity) {
+  if (err & ERR_NONE_MULTI)
+    return fail(OTSDB_E_ILLEGAL_DATA, "More than one value in aggregator raw");
+  if (err & ERR_RATE_TS)
+    return fail(OTSDB_E_ILLEGAL_STATE,
+                "Next timestamp is supposed to be strictly greater than the "
+                "previous one");
+  if (err & ERR_INFINITY)
+    return fail(OTSDB_E_ILLEGAL_STATE, "Got Infinity");
+  if (err & ERR_RAW_DUP)
+    return fail(OTSDB_E_UNSUPPORTED,
+                "raw group-by: timestamps decrease inside a span, or a "
+                "timestamp repeats more than 65,536 times");
+  if (err & ERR_X1_MASK)
+    return fail(OTSDB_E_ILLEGAL_STATE, "x1 beyond the millisecond mask");
+  if (err & ERR_SEL_TOO_BIG)
+    return fail(OTSDB_E_UNSUPPORTED,
+                "percentile/median over groups of more than %d series is not "
+                "offloaded yet", SEL_K);
+  if (err & ERR_CAL_RANGE)
+    return fail(OTSDB_E_UNSUPPORTED,
+                "a point past the window lies outside the calendar table");
+  if (err & ERR_INTERNAL)
+    return fail(OTSDB_E_DEVICE, "internal: bucket outside the group row");
+  if (total > capacity)
+    return fail(OTSDB_E_CAPACITY, "result capacity %lld < %lld points",
+                (long long)capacity, (long long)total);
+  return OTSDB_OK;
+}
 
 // reads the error word and the total point count; maps to a status
 otsdb_status finish(otsdb_ctx* c, int64_t G, otsdb_result* out) {
@@ -1593,101 +1400,6 @@ otsdb_status finish(otsdb_ctx* c, int64_t G, otsdb_result* out) {
   return rc;
 }
 
-// the status of one result: its device error word, then its capacity
-otsdb_status result_status(int err, int64_t total, int64_t capacity) {
-  if (err & ERR_NONE_MULTI)
-    return fail(OTSDB_E_ILLEGAL_DATA, "More than one value in aggregator raw");
-  if (err & ERR_RATE_TS)
-    return fail(OTSDB_E_ILLEGAL_STATE,
-                "Next timestamp is supposed to be strictly greater than the "
-                "previous one");
-  if (err & ERR_INFINITY)
-    return fail(OTSDB_E_ILLEGAL_STATE, "Got Infinity");
-  if (err & ERR_RAW_DUP)
-    return fail(OTSDB_E_UNSUPPORTED,
-                "raw group-by: timestamps decrease inside a span, or a "
-                "timestamp repeats more than 65,536 times");
-  if (err & ERR_X1_MASK)
-    return fail(OTSDB_E_ILLEGAL_STATE, "x1 beyond the millisecond mask");
-  if (err & ERR_SEL_TOO_BIG)
-    return fail(OTSDB_E_UNSUPPORTED,
-                "percentile/median over groups of more than %d series is not "
-                "offloaded yet", SEL_K);
-  if (err & ERR_CAL_RANGE)
-    return fail(OTSDB_E_UNSUPPORTED,
-                "a point past the window lies outside the calendar table");
-  if (err & ERR_INTERNAL)
-    return fail(OTSDB_E_DEVICE, "internal: bucket outside the group row");
-  if (total > capacity)
-    return fail(OTSDB_E_CAPACITY, "result capacity %lld < %lld points",
-                (long long)capacity, (long long)total);
-  return OTSDB_OK;
-}
-
-// a host entry's result too small: the caller still gets the offsets the
-// whole result needs (offsets[G] = its point count), then the status
-otsdb_status copy_offsets_back(otsdb_ctx* c, otsdb_result* out,
-                               const int64_t* d_offsets, int64_t G,
-                               otsdb_status rc) {
-  HIP_TRY(hipMemcpyAsync(out->offsets, d_offsets, 8 * (G + 1),
-                         hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return rc;
-}
-
-otsdb_status read_goff(otsdb_ctx* c, const otsdb_batch* b, bool device,
-                       std::vector<int64_t>& goff) {
-  goff.resize(b->n_groups + 1);
-  if (b->n_groups < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "n_groups < 0");
-  if (!b->group_offsets) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "no groups");
-  if (device && b->group_offsets_host) {
-    // the caller's host copy of the same offsets: no read-back, no sync
-    // (the caller keeps it equal to the device array: include/otsdb_agg.h)
-    memcpy(goff.data(), b->group_offsets_host, sizeof(int64_t) * goff.size());
-#ifdef OTSDB_DEBUG_SYNC
-    {  // debug builds: the host copy's total against the device's
-      int64_t last = 0;
-      HIP_TRY(hipMemcpyAsync(&last, b->group_offsets + b->n_groups,
-                             sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (last != goff.back())
-        return fail(OTSDB_E_ILLEGAL_ARGUMENT,
-                    "group_offsets_host[G] %lld != device %lld",
-                    (long long)goff.back(), (long long)last);
-    }
-#endif
-  } else if (device) {
-    HIP_TRY(hipMemcpyAsync(goff.data(), b->group_offsets,
-                           sizeof(int64_t) * goff.size(),
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  } else {
-    memcpy(goff.data(), b->group_offsets, sizeof(int64_t) * goff.size());
-  }
-  for (size_t i = 1; i < goff.size(); ++i)
-    if (goff[i] < goff[i - 1])
-      return fail(OTSDB_E_ILLEGAL_ARGUMENT, "group_offsets not monotonic");
-  return OTSDB_OK;
-}
-
-// A device entry's scope: the context locked, its device selected, the
-// caller's stream bound and the group offsets read (from the caller's host
-// copy where the batch has one), in that order.  rc: the first failure.
-struct DeviceCall {
-  CtxLock lk;
-  otsdb_status rc;
-  StreamBinding bind;
-  std::vector<int64_t> goff;
-  DeviceCall(otsdb_ctx* c, const otsdb_batch* b, void* hip_stream)
-      : lk(c), rc(select_device(c)), bind(c, hip_stream) {
-    if (!rc) rc = read_goff(c, b, true, goff);
-  }
-  static otsdb_status select_device(otsdb_ctx* c) {
-    HIP_TRY(hipSetDevice(c->device));
-    return OTSDB_OK;
-  }
-};
-
 // Raw (non-downsampled) group-by, raw.hip.  Device pointers throughout.
 otsdb_status run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
                      const otsdb_batch* b, const BatchDev& B,
@@ -1717,9 +1429,9 @@ otsdb_status run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
     counts = cv.take<int64_t>(G + 1);
     return cv.off + 256;
   };
-  otsdb_status rc = ensure(&c->ws, &c->ws_cap, carve1(nullptr));
+  otsdb_status rc = c->ws.ensure(carve1(nullptr));
   if (rc) return rc;
-  carve1((char*)c->ws);
+  carve1((char*)c->ws.p);
   HIP_TRY(hipMemsetAsync(c->d_err, 0, sizeof(int), st));
   if (G == 0) {
     HIP_TRY(hipMemsetAsync(out->offsets, 0, sizeof(int64_t), st));
@@ -1776,9 +1488,9 @@ otsdb_status run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
     tmp = cv.take<char>(sort_tmp + 1);
     return cv.off + 256;
   };
-  rc = ensure(&c->ws2, &c->ws2_cap, carve2(nullptr));
+  rc = c->ws2.ensure(carve2(nullptr));
   if (rc) return rc;
-  carve2((char*)c->ws2);
+  carve2((char*)c->ws2.p);
   if (M > 0)
     hipLaunchKernelGGL(k_raw_cand_fill, dim3(blocks_for(M, 4)), dim3(256), 0,
                        st, P, V, M, b->group_members, (const int64_t*)coff, kin,
@@ -1811,11 +1523,7 @@ otsdb_status run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
       // keys slab: one kmax-key row per block, at most 64 Mi keys per launch
       const int64_t per = std::max<int64_t>(
           1, std::min<int64_t>(n_out, ((int64_t)1 << 26) / std::max<int64_t>(kmax, 1)));
-      void* p = c->dec_ws;
-      size_t cap = c->dec_ws_cap;
-      rc = ensure(&p, &cap, (size_t)(per * std::max<int64_t>(kmax, 1)) * 8);
-      c->dec_ws = p;
-      c->dec_ws_cap = cap;
+      rc = c->dec_ws.ensure((size_t)(per * std::max<int64_t>(kmax, 1)) * 8);
       if (rc) return rc;
       for (int64_t u0 = 0; u0 < n_out; u0 += per) {
         const int64_t nb = std::min(per, n_out - u0);
@@ -1824,7 +1532,7 @@ otsdb_status run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
                            b->group_members, (const int32_t*)ugrp,
                            (const int32_t*)uocc, (const int64_t*)out->ts,
                            out->val, out->is_int,
-                           (uint64_t*)c->dec_ws, std::max<int64_t>(kmax, 1),
+                           (uint64_t*)c->dec_ws.p, std::max<int64_t>(kmax, 1),
                            c->d_err);
       }
     } else {
@@ -1843,14 +1551,6 @@ otsdb_status run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
   HIP_TRY(hipGetLastError());
   return finish(c, G, out);
 }
-
-otsdb_status run_device_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                             const otsdb_batch* b, otsdb_result* out,
-                             std::vector<int64_t>& goff);
-
-otsdb_status scan_excl(void* tmp, size_t tmp_bytes, const int64_t* in,
-                       int64_t* out, int64_t n, hipStream_t st);
-size_t scan_tmp_bytes(int64_t n, hipStream_t st);
 
 // FillingDownsampler over per-series grids (calendar.hip, stage A'): the
 // points whose own bucket starts on the filling grid, compacted, then the
@@ -1886,9 +1586,9 @@ otsdb_status run_anchored_fill(otsdb_ctx* c, const AnchoredPlan& A,
     return std::make_pair(cv.off + 256, std::vector<void*>{p[0], p[1], p[2], p[3],
                                                           p[4], p[5], p[6], t});
   };
-  otsdb_status rc = ensure(&c->acal_fill, &c->acal_fill_cap, carve(nullptr).first);
+  otsdb_status rc = c->acal_fill.ensure(carve(nullptr).first);
   if (rc) return rc;
-  auto q = carve((char*)c->acal_fill).second;
+  auto q = carve((char*)c->acal_fill.p).second;
   int64_t* fd = (int64_t*)q[0];
   uint8_t* on = (uint8_t*)q[1];
   int64_t* cnt = (int64_t*)q[2];
@@ -1959,9 +1659,9 @@ otsdb_status run_anchored(otsdb_ctx* c, const otsdb_query_spec* spec,
     p[7] = cv.take<int64_t>(std::max<int64_t>(N, 2));
     return std::make_pair(cv.off + 256, std::vector<void*>(p, p + 8));
   };
-  rc = ensure(&c->acal, &c->acal_cap, carve(nullptr).first);
+  rc = c->acal.ensure(carve(nullptr).first);
   if (rc) return rc;
-  auto pp = carve((char*)c->acal).second;
+  auto pp = carve((char*)c->acal.p).second;
   HIP_TRY(hipMemcpyAsync(pp[0], spec->cal_edges, 8 * n, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(pp[1], spec->cal_anchors, 8 * na, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(pp[2], spec->cal_anchor_edge, 8 * na,
@@ -1996,71 +1696,6 @@ otsdb_status run_anchored(otsdb_ctx* c, const otsdb_query_spec* spec,
   return run_device_impl(c, &A.derived, &vb, out, goff);
 }
 
-otsdb_status run_device_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                             const otsdb_batch* b, otsdb_result* out,
-                             std::vector<int64_t>& goff) {
-  otsdb_status rc = check_spec(spec);
-  if (rc) return rc;
-  if (anchored(spec)) return run_anchored(c, spec, b, out, goff);
-  Params P;
-  rc = make_params(spec, &P, c);
-  if (rc) return rc;
-  if (misaligned(b))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT,
-                "ts_ms/val must be 16-byte aligned (16-B streaming loads)");
-  const BatchDev B = batch_dev(b);
-  if (!(spec->ds_interval_ms > 0 || spec->run_all))
-    return run_raw(c, spec, b, B, goff, P, out);
-  Work W;
-  rc = run_pipeline(c, spec, B, b->group_members, goff, P, W, 0, nullptr,
-                    nullptr);
-  if (rc) return rc;
-  const int64_t G = (int64_t)goff.size() - 1;
-  rc = compact(c, P, G, W.out_val, W.out_emit, W.counts, out);
-  if (rc) return rc;
-  return finish(c, G, out);
-}
-
-// ------------------------------------------------------- rollup queries
-// otsdb_agg_run_rollup*: the points are a rollup table's cells; R (the
-// rollup aggregator) and the downsampling function F pick how a bucket is
-// computed (Downsampler.java:162-228, FillingDownsampler.java:196-252;
-// DESIGN.md §4.3).
-struct Rollup {
-  int32_t agg;         // R, RollupQuery.getRollupAgg()
-  const int64_t* cnt;  // every point's valueCount()
-};
-
-// The checks that need no device, and the state the rows are built with
-// (ROLLUP_NONE: the ordinary F.runDouble — the single query, counts ignored).
-otsdb_status check_rollup(const otsdb_query_spec* s, const Rollup& r,
-                          RollupKind* kind) {
-  if (r.agg < 0 || r.agg >= OTSDB_AGG_COUNT_IDS)
-    return fail(OTSDB_E_NO_SUCH_ELEMENT, "No such aggregator: %d", r.agg);
-  otsdb_status rc = check_spec(s);
-  if (rc) return rc;
-  if (r.agg == OTSDB_AGG_DEV)
-    return fail(OTSDB_E_UNSUPPORTED,
-                "standard deviation over rolled up data is not supported");
-  if (!(s->ds_interval_ms > 0 || s->run_all))
-    return fail(OTSDB_E_UNSUPPORTED, "a rollup query without a downsampler");
-  if (s->n_cal_anchors > 0)
-    return fail(OTSDB_E_UNSUPPORTED,
-                "rollup queries over per-series calendar anchors");
-  *kind = ROLLUP_NONE;
-  if (r.agg == OTSDB_AGG_AVG) {
-    if (s->ds_agg_id != OTSDB_AGG_AVG)
-      return fail(OTSDB_E_UNSUPPORTED,
-                  "rollup avg downsampled with another function");
-    if (!r.cnt)
-      return fail(OTSDB_E_ILLEGAL_ARGUMENT, "rollup avg needs value_count");
-    *kind = ROLLUP_AVG;
-  } else if (s->ds_agg_id == OTSDB_AGG_COUNT) {
-    *kind = ROLLUP_COUNT;
-  }
-  return OTSDB_OK;
-}
-
 // the context's rollup state for one call, cleared on every exit path
 struct RollupScope {
   otsdb_ctx* c;
@@ -2074,234 +1709,11 @@ struct RollupScope {
   }
 };
 
-// device pointers throughout (r.cnt too)
-otsdb_status run_rollup_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                             const otsdb_batch* b, const Rollup& r,
-                             otsdb_result* out, std::vector<int64_t>& goff) {
-  RollupKind kind;
-  otsdb_status rc = check_rollup(spec, r, &kind);
-  if (rc) return rc;
-  if (kind == ROLLUP_AVG && (((uintptr_t)r.cnt) & 15) != 0)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT,
-                "value_count must be 16-byte aligned (16-B streaming loads)");
-  RollupScope scope(c, kind, r.cnt);
-  return run_device_impl(c, spec, b, out, goff);
-}
-
-// ------------------------------------------ rollup queries from storage rows
-// otsdb_rollup_decode_rows_device / otsdb_agg_run_rollup_rows*: the rows of a
-// rollup table paired and decoded on the device (rollup_rows.hip, DESIGN.md
-// §4.3.1).
-otsdb_status check_rollup_table(const otsdb_raw_rows* raw,
-                                const otsdb_rollup_table* t, int32_t agg) {
-  if (!raw || !t) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  if (agg < 0 || agg >= OTSDB_AGG_COUNT_IDS)
-    return fail(OTSDB_E_NO_SUCH_ELEMENT, "No such aggregator: %d", agg);
-  if (agg == OTSDB_AGG_DEV)
-    return fail(OTSDB_E_UNSUPPORTED,
-                "standard deviation over rolled up data is not supported");
-  if (t->interval_s <= 0)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "rollup interval %d s", t->interval_s);
-  const bool avg = agg == OTSDB_AGG_AVG;
-  if (t->value_id < 0 || t->value_id > 127 ||
-      (avg && (t->count_id < 0 || t->count_id > 127)))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "rollup aggregator ids are 0..127");
-  if (raw->n_rows < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative n_rows");
-  if (!raw->row_series || !raw->row_base_s || !raw->row_col_off ||
-      !raw->col_qual_off || !raw->col_val_off ||
-      (raw->n_rows > 0 && (!raw->qual || !raw->val)))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null raw row array");
-  return OTSDB_OK;
-}
-
-// The decode without the lock (the contract of decode_impl: ts_ms null only
-// counts).  cnt may be null (R not avg: never written).
-otsdb_status rollup_decode_impl(otsdb_ctx* c, const otsdb_raw_rows* raw,
-                                const otsdb_rollup_table* t, int32_t agg,
-                                int64_t n_series, int64_t seek_ms,
-                                int64_t* offsets, int64_t* ts_ms, int64_t* val,
-                                uint8_t* is_float, int64_t* cnt,
-                                int64_t capacity, hipStream_t st,
-                                bool counted = false) {
-  const int64_t R = raw->n_rows, S = n_series;
-  if (S < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
-  RollupRowsDev T{};
-  T.R = R;
-  T.row_series = raw->row_series;
-  T.row_base_s = raw->row_base_s;
-  T.row_col_off = raw->row_col_off;
-  T.col_qoff = raw->col_qual_off;
-  T.qual = raw->qual;
-  T.col_voff = raw->col_val_off;
-  T.val = raw->val;
-  T.col_ts = raw->col_ts;
-  T.interval_ms = (int64_t)t->interval_s * 1000;
-  T.seek_ms = seek_ms;
-  T.need_count = agg == OTSDB_AGG_AVG;
-  T.value_id = t->value_id;
-  T.count_id = t->count_id;
-  T.fix = t->fix_duplicates != 0;
-  // RollupUtils.getRollupQualifierPrefix(R.toString()): lowercase + ':'
-  const char* name = kAggs[agg].name;
-  int pl = 0;
-  for (; name[pl] && pl < (int)sizeof(T.prefix) - 1; ++pl)
-    T.prefix[pl] = (uint8_t)tolower((unsigned char)name[pl]);
-  T.prefix[pl++] = ':';
-  T.prefix_len = pl;
-  const bool seek = T.need_count && seek_ms != INT64_MIN;
-  // workspace: row counts, row output offsets, last paired timestamps, the
-  // sought marks, the first error, the scan's temporary storage
-  const size_t tmpb = scan_tmp_bytes(R, st);
-  const size_t A = ((size_t)(R + 1) * 8 + 255) & ~(size_t)255;
-  otsdb_status rc = ensure(&c->dec_ws, &c->dec_ws_cap, 4 * A + 256 + tmpb);
-  if (rc) return rc;
-  char* w = (char*)c->dec_ws;
-  int64_t* row_count = (int64_t*)w;
-  int64_t* row_out = (int64_t*)(w + A);
-  int64_t* row_last = (int64_t*)(w + 2 * A);
-  uint8_t* sought = (uint8_t*)(w + 3 * A);
-  unsigned long long* first_err = (unsigned long long*)(w + 4 * A);
-  void* tmp = w + 4 * A + 256;
-  auto pass = [&](int mode) {
-    hipLaunchKernelGGL(k_rr_seq, dim3((unsigned)R), dim3(64), 0, st, T, mode,
-                       row_count, row_last,
-                       (const uint8_t*)(seek ? sought : nullptr),
-                       (const int64_t*)row_out, capacity, ts_ms, val, is_float,
-                       cnt, first_err);
-  };
-  // counted: an earlier call on the same rows (ts_ms null) left the row
-  // output offsets and the sought marks here: only the write pass runs, and
-  // the caller's pipeline follows it on the same stream (no synchronise)
-  if (counted) {
-    if (R > 0) pass(2);
-    HIP_TRY(hipGetLastError());
-    return OTSDB_OK;
-  }
-  HIP_TRY(hipMemsetAsync(first_err, 0xFF, 8, st));
-  HIP_TRY(hipMemsetAsync(row_count + R, 0, 8, st));
-  if (R > 0) {
-    pass(0);
-    if (seek) {
-      HIP_TRY(hipMemsetAsync(sought, 0, (size_t)R, st));
-      hipLaunchKernelGGL(k_rr_sought, dim3(blocks_for(R, 256)), dim3(256), 0,
-                         st, T, (const int64_t*)row_count,
-                         (const int64_t*)row_last, sought);
-      pass(1);
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  if ((rc = scan_excl(tmp, tmpb, row_count, row_out, R, st))) return rc;
-  hipLaunchKernelGGL(k_series_offsets, dim3(blocks_for(R + 1, 256)), dim3(256),
-                     0, st, R, S, raw->row_series, (const int64_t*)row_out,
-                     offsets);
-  HIP_TRY(hipMemcpyAsync(&c->h_small[0], first_err, 8, hipMemcpyDeviceToHost,
-                         st));
-  HIP_TRY(hipMemcpyAsync(&c->h_small[1], row_out + R, 8, hipMemcpyDeviceToHost,
-                         st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const unsigned long long fe = (unsigned long long)c->h_small[0];
-  if (fe != ~0ULL) {
-    const long long row = (long long)(fe >> 8);
-    switch ((int)(fe & 0xFF)) {
-      case RR_ILLEGAL_DATA:
-        return fail(OTSDB_E_ILLEGAL_DATA,
-                    "rollup row %lld: a cell of another aggregator, a value "
-                    "offset going back, or value bytes that do not match the "
-                    "qualifier", row);
-      case RR_ILLEGAL_ARGUMENT:
-        return fail(OTSDB_E_ILLEGAL_ARGUMENT,
-                    "rollup row %lld: a count offset is <= the last offset",
-                    row);
-      default:
-        return fail(OTSDB_E_UNSUPPORTED,
-                    "rollup row %lld: a millisecond qualifier, more than %d "
-                    "columns, or base times that do not increase", row,
-                    kRrRowCols);
-    }
-  }
-  const int64_t total = c->h_small[1];
-  if (!ts_ms) return OTSDB_OK;
-  if (total > capacity)
-    return fail(OTSDB_E_CAPACITY, "decode capacity %lld < %lld points",
-                (long long)capacity, (long long)total);
-  if (R > 0) pass(2);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
-  return OTSDB_OK;
-}
-
-// The timestamp the query's downsampler hands its source
-// (Downsampler.seekInterval, Downsampler.java:412-434): "all" seeks to the
-// window's start as given, a calendar to the first edge at or after it, a
-// fixed interval to the start rounded up to a multiple of it.
-int64_t rollup_seek_ms(const otsdb_query_spec* s) {
-  if (s->run_all) return s->start_ms;
-  if (s->use_calendar && s->cal_edges && s->n_cal_edges > 0) {
-    const int64_t* e = s->cal_edges;
-    const int64_t* p = std::lower_bound(e, e + s->n_cal_edges, s->start_ms);
-    return p == e + s->n_cal_edges ? s->start_ms : *p;
-  }
-  const int64_t iv = s->ds_interval_ms;
-  return align_down(s->start_ms + iv - 1, iv);
-}
-
-// device pointers throughout: the rows decoded into the context's columnar
-// buffer, then otsdb_agg_run_rollup_device's pipeline over it
-otsdb_status run_rollup_rows_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                                  const otsdb_raw_rows* raw,
-                                  const otsdb_rollup_table* t, int32_t agg,
-                                  const otsdb_batch* b, otsdb_result* out,
-                                  std::vector<int64_t>& goff) {
-  hipStream_t st = c->stream;
-  const int64_t S = b->n_series;
-  otsdb_status rc =
-      ensure(&c->cells_ws, &c->cells_ws_cap, (size_t)(S + 1) * 8 + 64);
-  if (rc) return rc;
-  int64_t* offs = (int64_t*)c->cells_ws;
-  const int64_t seek_ms = rollup_seek_ms(spec);
-  // the decode (its own stage; released before the pipeline)
-  std::unique_ptr<StageTimer> dec_tm(new StageTimer(c, 7));
-  rc = rollup_decode_impl(c, raw, t, agg, S, seek_ms, offs, nullptr, nullptr,
-                          nullptr, nullptr, 0, st);
-  if (rc) return rc;
-  const int64_t N = c->h_small[1];
-  const size_t col = ((size_t)std::max<int64_t>(N, 2) * 8 + 255) & ~(size_t)255;
-  rc = ensure(&c->cells_col, &c->cells_col_cap, 4 * col + 256);
-  if (rc) return rc;
-  int64_t* ts = (int64_t*)c->cells_col;
-  int64_t* vv = (int64_t*)((char*)c->cells_col + col);
-  int64_t* cnt = (int64_t*)((char*)c->cells_col + 2 * col);
-  uint8_t* isf = (uint8_t*)((char*)c->cells_col + 3 * col);
-  rc = rollup_decode_impl(c, raw, t, agg, S, seek_ms, offs, ts, vv, isf, cnt, N,
-                          st, true);
-  dec_tm.reset();
-  if (rc) return rc;
-  otsdb_batch cb = *b;
-  cb.n_points = N;
-  cb.offsets = offs;
-  cb.ts_ms = ts;
-  cb.val = vv;
-  cb.is_float = isf;
-  cb.series_float = nullptr;
-  return run_rollup_impl(c, spec, &cb, Rollup{agg, cnt}, out, goff);
-}
-
 // ----------------------------------- multi-aggregator and panel queries
 // otsdb_agg_run_multi*: n outputs that differ in the cross-series aggregator
 // (and its interpolation) over one query.  DESIGN.md §4.
 // otsdb_agg_run_panel*: they differ in the downsampling function as well
 // (ds set).  DESIGN.md §4.2.
-struct Req {
-  int32_t n;
-  const int32_t* ds;  // null: every output downsamples with spec->ds_agg_id
-  const int32_t* aggs;
-  const int32_t* interps;  // null: every output its aggregator's own
-  otsdb_result* outs;
-  // the request's first error word / compaction slot (d_merr, h_mdone): the
-  // functions of a panel call run as one request each over one set of slots
-  int32_t e0 = 0;
-};
-
 otsdb_query_spec req_spec(const otsdb_query_spec* s, const Req& q, int i) {
   otsdb_query_spec r = *s;
   if (q.ds) r.ds_agg_id = q.ds[i];
@@ -2543,11 +1955,11 @@ otsdb_status multi_build(otsdb_ctx* c, const otsdb_query_spec* spec,
   if (part) {
     part->ws_need = carve(nullptr);
     if (part->size_only) return OTSDB_OK;
-    carve((char*)c->ws + part->ws_off);
+    carve((char*)c->ws.p + part->ws_off);
   } else {
-    rc = ensure(&c->ws, &c->ws_cap, carve(nullptr));
+    rc = c->ws.ensure(carve(nullptr));
     if (rc) return rc;
-    carve((char*)c->ws);
+    carve((char*)c->ws.p);
 
     // every output its own error word; the shared stages report into the
     // context's (folded into every output's status at the end)
@@ -3005,9 +2417,9 @@ otsdb_status multi_fold_pass(otsdb_ctx* c, const otsdb_query_spec* s0,
     if (two_level) carve_combine(cv, W, T.MG, NB);
     return cv.off + 256;
   };
-  rc = ensure(&c->ws, &c->ws_cap, carve(nullptr));
+  rc = c->ws.ensure(carve(nullptr));
   if (rc) return rc;
-  carve((char*)c->ws);
+  carve((char*)c->ws.p);
   W.R = Rows{nullptr, nullptr};
   W.partial = nullptr;
   W.out_val = nullptr;
@@ -3237,7 +2649,7 @@ otsdb_status panel_build(otsdb_ctx* c, PanelPass& X, const BatchDev& B,
   size_t total = 0;
   for (int pass = 0; pass < 2; ++pass) {
     if (pass == 1) {
-      rc = ensure(&c->ws, &c->ws_cap, total);
+      rc = c->ws.ensure(total);
       if (rc) return rc;
     }
     size_t off = 0;
@@ -3417,9 +2829,9 @@ otsdb_status decode_impl(otsdb_ctx* c, const otsdb_cells* cells,
                                   (size_t)(R + 1), rocprim::plus<int64_t>(),
                                   st));
   const size_t ws_need = (size_t)(2 * R + 2) * 8 + (size_t)R + 128 + scan_tmp;
-  otsdb_status rc = ensure(&c->dec_ws, &c->dec_ws_cap, ws_need);
+  otsdb_status rc = c->dec_ws.ensure(ws_need);
   if (rc) return rc;
-  int64_t* row_count = (int64_t*)c->dec_ws;
+  int64_t* row_count = (int64_t*)c->dec_ws.p;
   int64_t* row_out = row_count + (R + 1);
   uint8_t* fast = (uint8_t*)(row_out + (R + 1));
   int* flags = (int*)(((uintptr_t)(fast + R) + 15) & ~(uintptr_t)15);
@@ -3500,10 +2912,9 @@ otsdb_status requal_impl(otsdb_ctx* c, const CellsDev& C, CellsDev* out,
                                   (int64_t*)nullptr, (int64_t)0,
                                   (size_t)(R + 1), rocprim::plus<int64_t>(),
                                   st));
-  otsdb_status rc = ensure(&c->dec_ws, &c->dec_ws_cap,
-                           (size_t)(2 * R + 2) * 8 + 128 + scan_tmp);
+  otsdb_status rc = c->dec_ws.ensure((size_t)(2 * R + 2) * 8 + 128 + scan_tmp);
   if (rc) return rc;
-  int64_t* row_count = (int64_t*)c->dec_ws;
+  int64_t* row_count = (int64_t*)c->dec_ws.p;
   int64_t* row_out = row_count + (R + 1);
   void* tmp = (void*)(((uintptr_t)(row_out + R + 1) + 63) & ~(uintptr_t)63);
   HIP_TRY(hipMemsetAsync(c->d_err, 0, sizeof(int), st));
@@ -3526,10 +2937,10 @@ otsdb_status requal_impl(otsdb_ctx* c, const CellsDev& C, CellsDev* out,
                 "Corrupted value: couldn't break down into individual values");
   const int64_t N = c->h_small[1];
   const size_t qo = ((size_t)(R + 1) * 8 + 255) & ~(size_t)255;
-  rc = ensure(&c->cells_col, &c->cells_col_cap, qo + 4 * (size_t)N + 64);
+  rc = c->cells_col.ensure(qo + 4 * (size_t)N + 64);
   if (rc) return rc;
-  int64_t* qoff = (int64_t*)c->cells_col;
-  uint8_t* qual = (uint8_t*)c->cells_col + qo;
+  int64_t* qoff = (int64_t*)c->cells_col.p;
+  uint8_t* qual = (uint8_t*)c->cells_col.p + qo;
   if (R > 0)
     hipLaunchKernelGGL(k_requal<1>, dim3(blocks_for(R, 4 * OTSDB_RQ_RPW)), dim3(256), 0, st,
                        C, row_count, (const int64_t*)row_out, qoff, qual,
@@ -3541,8 +2952,42 @@ otsdb_status requal_impl(otsdb_ctx* c, const CellsDev& C, CellsDev* out,
   return OTSDB_OK;
 }
 
+// The compacted columns decoded into the context's own columnar buffer: *cb
+// is b over them (the fallback of the fused cells queries).
 otsdb_status cells_columnar(otsdb_ctx* c, const otsdb_cells* cells,
-                            const otsdb_batch* b, otsdb_batch* cb_out);
+                            const otsdb_batch* b, otsdb_batch* cb_out) {
+  hipStream_t st = c->stream;
+  const int64_t S = b->n_series;
+  otsdb_status rc =
+      c->cells_ws.ensure((size_t)(S + 1) * 8 + 64);
+  if (rc) return rc;
+  int64_t* offs = (int64_t*)c->cells_ws.p;
+  // the generic decode (its own stage; released before the pipeline)
+  std::unique_ptr<StageTimer> dec_tm(new StageTimer(c, 7));
+  rc = decode_impl(c, cells, S, offs, nullptr, nullptr, nullptr, 0, st);
+  if (rc) return rc;
+  int64_t N = 0;
+  HIP_TRY(hipMemcpyAsync(&N, offs + S, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const size_t col = ((size_t)std::max<int64_t>(N, 2) * 8 + 255) & ~(size_t)255;
+  rc = c->cells_col.ensure(2 * col + (size_t)std::max<int64_t>(N, 2) + 256);
+  if (rc) return rc;
+  int64_t* ts = (int64_t*)c->cells_col.p;
+  int64_t* vv = (int64_t*)((char*)c->cells_col.p + col);
+  uint8_t* isf = (uint8_t*)((char*)c->cells_col.p + 2 * col);
+  rc = decode_impl(c, cells, S, offs, ts, vv, isf, N, st, true);
+  dec_tm.reset();
+  if (rc) return rc;
+  otsdb_batch cb = *b;
+  cb.n_points = N;
+  cb.offsets = offs;
+  cb.ts_ms = ts;
+  cb.val = vv;
+  cb.is_float = isf;
+  cb.series_float = nullptr;
+  *cb_out = cb;
+  return OTSDB_OK;
+}
 
 // The fused cells path with its retries, for every cells query.  pass(CQ,
 // series_row): one attempt's launches over the columns CQ; finish(): the
@@ -3564,9 +3009,9 @@ otsdb_status cells_attempts(otsdb_ctx* c, const otsdb_cells* cells, int64_t S,
   hipStream_t st = c->stream;
   const int64_t R = cells->n_rows;
   *end = CELLS_DONE;
-  otsdb_status rc = ensure(&c->cells_ws, &c->cells_ws_cap, (size_t)(S + 1) * 8);
+  otsdb_status rc = c->cells_ws.ensure((size_t)(S + 1) * 8);
   if (rc) return rc;
-  int64_t* series_row = (int64_t*)c->cells_ws;
+  int64_t* series_row = (int64_t*)c->cells_ws.p;
   hipLaunchKernelGGL(k_series_rows, dim3(blocks_for(R + 1, 256)), dim3(256),
                      0, st, R, S, cells->row_series, series_row);
   P.check_order = c->verbatim ? 1 : 0;
@@ -3609,80 +3054,6 @@ otsdb_status cells_attempts(otsdb_ctx* c, const otsdb_cells* cells, int64_t S,
   return OTSDB_OK;
 }
 
-// Query straight from compacted columns: the fused decode + downsample when
-// the query and the columns allow it, else decode -> columnar -> pipeline.
-// mq: several aggregators (otsdb_agg_run_cells_multi_device; `spec` carries
-// output 0's, `out` is unused): the same routing, with the shared-rows
-// pipeline in place of run_pipeline where the outputs can share them (with
-// OTSDB_SPEC_CELLS_MULTI_FOLD on an eligible request: the cells fold over
-// the envelope state in its place, multi_fold_pass), and run_multi_impl over
-// the decoded columns otherwise (never folded).
-otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                            const otsdb_cells* cells, const otsdb_batch* b,
-                            otsdb_result* out, std::vector<int64_t>& goff,
-                            const Req* mq = nullptr) {
-  otsdb_status rc = check_spec(spec);
-  if (rc) return rc;
-  const int64_t S = b->n_series, R = cells->n_rows;
-  if (S < 0 || R < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
-  const bool ds = spec->ds_interval_ms > 0 || spec->run_all;
-  Params P;
-  // per-series calendar grids rewrite columnar timestamps: decode first
-  const bool fused = ds && !anchored(spec);
-  if (fused) {
-    rc = make_params(spec, &P, c);
-    if (rc) return rc;
-  }
-  if (fused && !P.ds_sel && !P.run_all &&
-      (!mq || multi_shares_rows(spec, *mq, P, S, goff))) {
-    const BatchDev B{S, nullptr, nullptr, nullptr, nullptr, nullptr};
-    Work W;
-    MultiState MS;
-    MultiFoldRun MF;
-    CellsEnd end;
-    // OTSDB_SPEC_CELLS_MULTI_FOLD: the cells fold over the envelope state in
-    // the row pass's place (narrow grids, as the single cells fold; calendar
-    // grids from cells keep the rows)
-    const bool mfold = mq && !c->verbatim && P.narrow &&
-                       multi_folds(spec, *mq, P, OTSDB_SPEC_CELLS_MULTI_FOLD);
-    if (mq) c->n_multi_fold = 0;
-    rc = cells_attempts(
-        c, cells, S, P, &end,
-        [&](const CellsDev& CQ, const int64_t* series_row) {
-          if (mfold)
-            return multi_fold_pass(c, spec, *mq, B, b->group_members, goff, P,
-                                   &CQ, series_row, MF);
-          if (mq) {  // (every attempt its own work set)
-            MS = MultiState();
-            return multi_build(c, spec, *mq, B, b->group_members, goff, P, &CQ,
-                               series_row, MS);
-          }
-          W = Work();
-          return run_pipeline(c, spec, B, b->group_members, goff, P, W, 0,
-                              nullptr, nullptr, &CQ, series_row);
-        },
-        [&]() {
-          if (mfold) return multi_fold_finish(c, *mq, MF);
-          if (mq) return multi_aggregate(c, MS);
-          const int64_t G = (int64_t)goff.size() - 1;
-          const otsdb_status rf =
-              compact(c, P, G, W.out_val, W.out_emit, W.counts, out);
-          return rf ? rf : finish(c, G, out);
-        });
-    if (rc || end != CELLS_DECODE) return rc;
-  }
-  // (verbatim storage rows take only the cells fold)
-  if (c->verbatim) return spec_miss(c);
-  // decode to a columnar batch in the context's own buffer, then the
-  // columnar pipeline (raw group-by, median/percentile or "all" downsampling,
-  // mixed-width columns)
-  otsdb_batch cb;
-  rc = cells_columnar(c, cells, b, &cb);
-  if (rc) return rc;
-  if (mq) return run_multi_impl(c, spec, *mq, &cb, goff, /*may_fold=*/false);
-  return run_device_impl(c, spec, &cb, out, goff);
-}
-
 // One cells call for a request without downsampling functions: the single
 // query, unchanged, for one output, else the cells multi call.
 otsdb_status run_cells_req(otsdb_ctx* c, const otsdb_query_spec* spec,
@@ -3695,44 +3066,6 @@ otsdb_status run_cells_req(otsdb_ctx* c, const otsdb_query_spec* spec,
   const otsdb_status rc = run_cells_impl(c, &s0, cells, b, &q.outs[0], goff);
   if (!rc) c->multi_total[0] = c->h_small[1];
   return rc;
-}
-
-// The compacted columns decoded into the context's own columnar buffer: *cb
-// is b over them (the fallback of the fused cells queries).
-otsdb_status cells_columnar(otsdb_ctx* c, const otsdb_cells* cells,
-                            const otsdb_batch* b, otsdb_batch* cb_out) {
-  hipStream_t st = c->stream;
-  const int64_t S = b->n_series;
-  otsdb_status rc =
-      ensure(&c->cells_ws, &c->cells_ws_cap, (size_t)(S + 1) * 8 + 64);
-  if (rc) return rc;
-  int64_t* offs = (int64_t*)c->cells_ws;
-  // the generic decode (its own stage; released before the pipeline)
-  std::unique_ptr<StageTimer> dec_tm(new StageTimer(c, 7));
-  rc = decode_impl(c, cells, S, offs, nullptr, nullptr, nullptr, 0, st);
-  if (rc) return rc;
-  int64_t N = 0;
-  HIP_TRY(hipMemcpyAsync(&N, offs + S, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const size_t col = ((size_t)std::max<int64_t>(N, 2) * 8 + 255) & ~(size_t)255;
-  rc = ensure(&c->cells_col, &c->cells_col_cap,
-              2 * col + (size_t)std::max<int64_t>(N, 2) + 256);
-  if (rc) return rc;
-  int64_t* ts = (int64_t*)c->cells_col;
-  int64_t* vv = (int64_t*)((char*)c->cells_col + col);
-  uint8_t* isf = (uint8_t*)((char*)c->cells_col + 2 * col);
-  rc = decode_impl(c, cells, S, offs, ts, vv, isf, N, st, true);
-  dec_tm.reset();
-  if (rc) return rc;
-  otsdb_batch cb = *b;
-  cb.n_points = N;
-  cb.offsets = offs;
-  cb.ts_ms = ts;
-  cb.val = vv;
-  cb.is_float = isf;
-  cb.series_float = nullptr;
-  *cb_out = cb;
-  return OTSDB_OK;
 }
 
 // One attempt of the shared cells pass: the functions' buffers, the state
@@ -3848,810 +3181,335 @@ otsdb_status run_cells_panel_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
   return run_panel_impl(c, spec, q, &cb, goff);
 }
 
-// ----------------------------------------- storage rows -> compacted rows
-otsdb_status row_status(otsdb_ctx*, unsigned long long fe, const char* what) {
-  if (fe == ~0ULL) return OTSDB_OK;
-  const int code = (int)(fe & 0xFF);
-  const long long row = (long long)(fe >> 8);
-  switch (code) {
-    case RS_ILLEGAL_ARGUMENT:
-      return fail(OTSDB_E_ILLEGAL_ARGUMENT,
-                  "%s row %lld: Can not parse cell, it is not an appended cell",
-                  what, row);
-    case RS_UNSUPPORTED:
-      return fail(OTSDB_E_UNSUPPORTED,
-                  "%s row %lld: more than %d points or %d data columns to "
-                  "merge, or appended points beside a column out of time order",
-                  what, row, kRowCellCap, kRowColCap);
-    default:
-      return fail(OTSDB_E_ILLEGAL_DATA,
-                  "%s row %lld: corrupted value or duplicate timestamp", what,
-                  row);
-  }
-}
-
-// one exclusive scan of n + 1 int64 (in[n] must be 0), on st
-otsdb_status scan_excl(void* tmp, size_t tmp_bytes, const int64_t* in,
-                       int64_t* out, int64_t n, hipStream_t st) {
-  size_t t = tmp_bytes;
-  HIP_TRY(rocprim::exclusive_scan(tmp, t, in, out, (int64_t)0, (size_t)(n + 1),
-                                  rocprim::plus<int64_t>(), st));
-  return OTSDB_OK;
-}
-
-size_t scan_tmp_bytes(int64_t n, hipStream_t st) {
-  size_t b = 0;
-  rocprim::exclusive_scan(nullptr, b, (const int64_t*)nullptr, (int64_t*)nullptr,
-                          (int64_t)0, (size_t)(n + 1), rocprim::plus<int64_t>(),
-                          st);
-  return (b + 255) & ~(size_t)255;
-}
-
-// CompactionQueue.compact of every storage row (rows.hip).  Output: the kept
-// rows' compacted columns packed in row order, *n_out rows; *qbytes / *vbytes
-// the bytes written.
-otsdb_status cells_buffer(otsdb_ctx* c, int which, int64_t R, int64_t qb,
-                          int64_t vb, otsdb_cells_out* o);
-
-// own >= 0: the output goes to the context's cells buffer `own`, returned in
-// *owned (o is ignored)
-// LARGE rows (rows.hip): rank the columns, record the cells, sort the keys,
-// merge — through global memory, one segment per row
-otsdb_status compact_large(otsdb_ctx* c, const RawDev& D, int fix,
-                           const LargeSlots& LS, int64_t n_large, int64_t NC,
-                           int64_t ncell, const int64_t* gen_base,
-                           const int64_t* gen_n, CellRec* rec, uint8_t* stq,
-                           uint8_t* stv, int64_t* out_q, int64_t* out_v,
-                           unsigned long long* first_err, hipStream_t st) {
-  if (NC >= (int64_t(1) << 32) || ncell >= (int64_t(1) << 32))
-    return fail(OTSDB_E_UNSUPPORTED, "compaction of %lld cells in large rows",
-                (long long)ncell);
-  size_t t_pairs = 0, t_keys = 0;
-  HIP_TRY(rocprim::segmented_radix_sort_pairs(
-      nullptr, t_pairs, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-      (const int64_t*)nullptr, (int64_t*)nullptr, (unsigned)NC,
-      (unsigned)n_large, (const int64_t*)nullptr, (const int64_t*)nullptr, 0,
-      64, st));
-  HIP_TRY(rocprim::segmented_radix_sort_keys(
-      nullptr, t_keys, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-      (unsigned)ncell, (unsigned)n_large, (const int64_t*)nullptr,
-      (const int64_t*)nullptr, 0, kLargeKeyBits, st));
-  const size_t t_scan = scan_tmp_bytes(NC, st);
-  const size_t t_sort = std::max(std::max(t_pairs, t_keys), t_scan);
-  uint64_t *ckey, *ckey2, *rkey, *rkey2;
-  int64_t *cidx, *cidx2, *cslot, *ccount, *cbase, *segb, *sege;
-  int* bad;
-  void* tmp;
-  auto carve = [&](char* base) {
-    Carve cv{base};
-    ckey = cv.take<uint64_t>(NC);
-    ckey2 = cv.take<uint64_t>(NC);
-    cidx = cv.take<int64_t>(NC);
-    cidx2 = cv.take<int64_t>(NC);
-    cslot = cv.take<int64_t>(NC);
-    ccount = cv.take<int64_t>(NC + 1);
-    cbase = cv.take<int64_t>(NC + 1);
-    segb = cv.take<int64_t>(n_large);
-    sege = cv.take<int64_t>(n_large);
-    bad = cv.take<int>(n_large);
-    rkey = cv.take<uint64_t>(ncell);
-    rkey2 = cv.take<uint64_t>(ncell);
-    tmp = cv.take<char>(t_sort + 1);
-    return cv.off + 256;
-  };
-  otsdb_status rc = ensure(&c->rows_large, &c->rows_large_cap, carve(nullptr));
-  if (rc) return rc;
-  carve((char*)c->rows_large);
-  hipLaunchKernelGGL(k_large_cols, dim3(blocks_for(n_large, 4)), dim3(256), 0,
-                     st, D, LS, n_large, ckey, cidx, cslot, segb, sege);
-  size_t t = t_sort;
-  HIP_TRY(rocprim::segmented_radix_sort_pairs(
-      tmp, t, (const uint64_t*)ckey, ckey2, (const int64_t*)cidx, cidx2,
-      (unsigned)NC, (unsigned)n_large, (const int64_t*)segb,
-      (const int64_t*)sege, 0, 64, st));
-  HIP_TRY(hipMemsetAsync(ccount + NC, 0, 8, st));
-  const unsigned wblocks = blocks_for((NC + 63) / 64, 4);
-  hipLaunchKernelGGL(k_large_recs, dim3(wblocks), dim3(256), 0, st, D, LS, NC,
-                     (const int64_t*)cidx2, (const int64_t*)cslot, gen_base,
-                     ccount, (const int64_t*)nullptr, rec, rkey, bad, 0);
-  if ((rc = scan_excl(tmp, t_sort, ccount, cbase, NC, st))) return rc;
-  HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int) * n_large, st));
-  hipLaunchKernelGGL(k_large_recs, dim3(wblocks), dim3(256), 0, st, D, LS, NC,
-                     (const int64_t*)cidx2, (const int64_t*)cslot, gen_base,
-                     ccount, (const int64_t*)cbase, rec, rkey, bad, 1);
-  hipLaunchKernelGGL(k_large_segs, dim3(blocks_for(n_large, 256)), dim3(256),
-                     0, st, LS, n_large, gen_base, gen_n, segb, sege);
-  t = t_sort;
-  HIP_TRY(rocprim::segmented_radix_sort_keys(
-      tmp, t, (const uint64_t*)rkey, rkey2, (unsigned)ncell,
-      (unsigned)n_large, (const int64_t*)segb, (const int64_t*)sege, 0,
-      kLargeKeyBits, st));
-  // (rkey, free after the sort, holds the heap order of rows with unsorted
-  // columns)
-  hipLaunchKernelGGL(k_large_merge, dim3((unsigned)n_large), dim3(64), 0, st,
-                     D, fix, LS, gen_base, gen_n, (const CellRec*)rec,
-                     (const uint64_t*)rkey2, (const int*)bad, rkey, stq, stv,
-                     out_q, out_v, first_err);
-  HIP_TRY(hipGetLastError());
-  return OTSDB_OK;
-}
-
-otsdb_status compact_impl(otsdb_ctx* c, const otsdb_raw_rows* raw, int fix,
-                          const otsdb_cells_out* o, int64_t qcap, int64_t vcap,
-                          int64_t* n_out, int64_t* qbytes, int64_t* vbytes,
-                          hipStream_t st, int own = -1,
-                          otsdb_cells_out* owned = nullptr) {
-  const int64_t R = raw->n_rows;
-  if (R < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative n_rows");
-  if (!raw->row_base_s || !raw->row_col_off || !raw->col_qual_off ||
-      !raw->col_val_off || (R > 0 && (!raw->qual || !raw->val)))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null raw row array");
-  RawDev D{R, raw->row_col_off, raw->col_qual_off, raw->qual, raw->col_val_off,
-           raw->val, raw->col_ts};
-  const size_t tmpb = scan_tmp_bytes(R, st);
-  const size_t A = ((size_t)(R + 1) * 8 + 255) & ~(size_t)255;
-  // kind, lone, gen_n, gen_base, out_q, out_v, kept, oq_off, ov_off, k_off,
-  // LARGE slots (row, columns, ranked-column base), first_err, counters,
-  // scan temp
-  const size_t need = 13 * A + 512 + tmpb;
-  otsdb_status rc = ensure(&c->rows_ws, &c->rows_ws_cap, need);
-  if (rc) return rc;
-  char* w = (char*)c->rows_ws;
-  uint8_t* kind = (uint8_t*)w;
-  int64_t* lone = (int64_t*)(w + A);
-  int64_t* gen_n = (int64_t*)(w + 2 * A);
-  int64_t* gen_base = (int64_t*)(w + 3 * A);
-  int64_t* out_q = (int64_t*)(w + 4 * A);
-  int64_t* out_v = (int64_t*)(w + 5 * A);
-  int64_t* kept = (int64_t*)(w + 6 * A);
-  int64_t* oq_off = (int64_t*)(w + 7 * A);
-  int64_t* ov_off = (int64_t*)(w + 8 * A);
-  int64_t* k_off = (int64_t*)(w + 9 * A);
-  LargeSlots LS{(unsigned long long*)(w + 13 * A + 256), (int64_t*)(w + 10 * A),
-                (int64_t*)(w + 11 * A), (int64_t*)(w + 12 * A)};
-  unsigned long long* first_err = (unsigned long long*)(w + 13 * A);
-  void* tmp = w + 13 * A + 512;
-  HIP_TRY(hipMemsetAsync(first_err, 0xFF, 8, st));
-  HIP_TRY(hipMemsetAsync(LS.ctr, 0, 16, st));
-  for (int64_t* a : {gen_n, out_q, out_v, kept})
-    HIP_TRY(hipMemsetAsync(a + R, 0, 8, st));
-  if (R > 0) {
-    // the verbatim columns first (64 rows a wavefront), the exact plan only
-    // when some row is left (a flag read: one sync)
-    int* pend = (int*)(LS.ctr + 8);
-    HIP_TRY(hipMemsetAsync(pend, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_rows_uniform, dim3(blocks_for(R, 256)), dim3(256), 0,
-                       st, D, kind, lone, gen_n, out_q, out_v, kept, pend);
-    int hp = 0;
-    HIP_TRY(hipMemcpyAsync(&hp, pend, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (hp)
-      hipLaunchKernelGGL(k_rows_plan, dim3(blocks_for(R, 4)), dim3(256), 0, st,
-                         D, fix, kind, lone, gen_n, out_q, out_v, kept,
-                         first_err, LS);
-  }
-  HIP_TRY(hipGetLastError());
-  if ((rc = scan_excl(tmp, tmpb, gen_n, gen_base, R, st))) return rc;
-  HIP_TRY(hipMemcpyAsync(&c->h_small[0], gen_base + R, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(&c->h_small[5], LS.ctr, 16, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const int64_t ncell = c->h_small[0];
-  const int64_t n_large = c->h_small[5], NC = c->h_small[6];
-  if (ncell > 0) {
-    const size_t recb = ((size_t)ncell * sizeof(CellRec) + 255) & ~(size_t)255;
-    const size_t qb = ((size_t)ncell * 4 + 255) & ~(size_t)255;
-    rc = ensure(&c->rows_scr, &c->rows_scr_cap, recb + qb + (size_t)ncell * 9 + 256);
-    if (rc) return rc;
-    CellRec* rec = (CellRec*)c->rows_scr;
-    uint8_t* stq = (uint8_t*)c->rows_scr + recb;
-    uint8_t* stv = stq + qb;
-    hipLaunchKernelGGL(k_rows_general, dim3((unsigned)R), dim3(64), 0, st, D, fix,
-                       (const uint8_t*)kind, (const int64_t*)gen_base, rec, stq,
-                       stv, out_q, out_v, first_err);
-    HIP_TRY(hipGetLastError());
-    if (n_large > 0 &&
-        (rc = compact_large(c, D, fix, LS, n_large, NC, ncell, gen_base, gen_n,
-                            rec, stq, stv, out_q, out_v, first_err, st)))
-      return rc;
-  }
-  HIP_TRY(hipMemcpyAsync(&c->h_small[1], first_err, 8, hipMemcpyDeviceToHost, st));
-  if ((rc = scan_excl(tmp, tmpb, out_q, oq_off, R, st))) return rc;
-  if ((rc = scan_excl(tmp, tmpb, out_v, ov_off, R, st))) return rc;
-  if ((rc = scan_excl(tmp, tmpb, kept, k_off, R, st))) return rc;
-  HIP_TRY(hipMemcpyAsync(&c->h_small[2], oq_off + R, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(&c->h_small[3], ov_off + R, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(&c->h_small[4], k_off + R, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  rc = row_status(c, (unsigned long long)c->h_small[1], "storage");
-  if (rc) return rc;
-  const int64_t tq = c->h_small[2], tv = c->h_small[3], nk = c->h_small[4];
-  *n_out = nk;
-  if (qbytes) *qbytes = tq;
-  if (vbytes) *vbytes = tv;
-  int bytes = 1;
-  if (own >= 0) {
-    if ((rc = cells_buffer(c, own, nk, 0, 0, owned))) return rc;
-    // an engine-owned output aliases the input pools when it can
-    // (k_rows_alias): the common scan of single compacted columns moves no
-    // value bytes
-    unsigned long long* acc = LS.ctr + 2;  // 5 words after the counters
-    const unsigned long long init[5] = {~0ULL, 0ULL, ~0ULL, 0ULL, 0ULL};
-    HIP_TRY(hipMemcpyAsync(acc, init, sizeof(init), hipMemcpyHostToDevice, st));
-    if (R > 0)
-      hipLaunchKernelGGL(k_rows_alias,
-                         dim3((unsigned)std::min<int64_t>(blocks_for(R, 256), 2048)),
-                         dim3(256), 0, st, D, (const uint8_t*)kind,
-                         (const int64_t*)lone, (const int64_t*)oq_off,
-                         (const int64_t*)ov_off, acc);
-    HIP_TRY(hipGetLastError());
-    unsigned long long h[5];
-    HIP_TRY(hipMemcpyAsync(h, acc, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (nk > 0 && h[4] == 0 && h[0] == h[1] && h[2] == h[3]) {
-      bytes = 0;
-      owned->qual = const_cast<uint8_t*>(raw->qual) + h[0];
-      owned->val = const_cast<uint8_t*>(raw->val) + h[2];
-    } else if ((rc = cells_buffer(c, own, nk, tq, tv, owned))) {
-      return rc;
-    }
-    o = owned;
-    qcap = tq;
-    vcap = tv;
-  }
-  if (!o) return OTSDB_OK;  // sizes only
-  if (tq > qcap || tv > vcap)
-    return fail(OTSDB_E_CAPACITY, "compaction output: %lld qualifier / %lld "
-                "value bytes, capacity %lld / %lld", (long long)tq,
-                (long long)tv, (long long)qcap, (long long)vcap);
-  if (!o->row_base_s || !o->qual_off || !o->val_off || !o->qual || !o->val)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null output array");
-  CellRec* rec = (CellRec*)c->rows_scr;
-  const size_t recb = ((size_t)ncell * sizeof(CellRec) + 255) & ~(size_t)255;
-  const size_t qb = ((size_t)ncell * 4 + 255) & ~(size_t)255;
-  const uint8_t* stq = ncell ? (uint8_t*)c->rows_scr + recb : nullptr;
-  const uint8_t* stv = ncell ? stq + qb : nullptr;
-  (void)rec;
-  if (R > 0 && nk > 0 && !bytes) {
-    hipLaunchKernelGGL(k_rows_meta, dim3(blocks_for(R, 256)), dim3(256), 0, st,
-                       R, raw->row_series, raw->row_base_s, (const uint8_t*)kind,
-                       (const int64_t*)oq_off, (const int64_t*)ov_off,
-                       (const int64_t*)k_off, o->row_series, o->row_base_s,
-                       o->qual_off, o->val_off);
-    HIP_TRY(hipGetLastError());
-  } else if (R > 0 && nk > 0) {
-    // row_series is optional on the output
-    hipLaunchKernelGGL(k_rows_write, dim3(blocks_for(R, 4)), dim3(256), 0, st,
-                       D, fix, raw->row_series, raw->row_base_s,
-                       (const uint8_t*)kind, (const int64_t*)lone,
-                       (const int64_t*)gen_base, stq, stv,
-                       (const int64_t*)out_q, (const int64_t*)out_v,
-                       (const int64_t*)oq_off, (const int64_t*)ov_off,
-                       (const int64_t*)k_off, o->row_series, o->row_base_s, o->qual_off, o->qual, o->val_off, o->val);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipMemcpyAsync(o->qual_off + nk, oq_off + R, 8, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(o->val_off + nk, ov_off + R, 8, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return OTSDB_OK;
-}
-
-// Span.addRow over every series' compacted rows (rows.hip).  *identity: no
-// series needed the replay (the output then equals the input and, when
-// o == nullptr, nothing is written).
-otsdb_status span_impl(otsdb_ctx* c, const otsdb_cells* in, int64_t S,
-                       const otsdb_cells_out* o, int64_t qcap, int64_t vcap,
-                       int64_t* n_out, int64_t* qbytes, int64_t* vbytes,
-                       bool* identity, hipStream_t st, int own = -1,
-                       otsdb_cells_out* owned = nullptr) {
-  const int64_t R = in->n_rows;
-  if (R < 0 || S < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
-  CellsDev C{R, in->row_series, in->row_base_s, in->qual_off, in->qual,
-             in->val_off, in->val};
-  const size_t tmpb = scan_tmp_bytes(S, st);
-  const size_t A = ((size_t)(S + 1) * 8 + 255) & ~(size_t)255;
-  // series_row, slow, arena_sz, arena_off, o_rows, o_q, o_v, row_off, q_off,
-  // v_off, err word, scan temp
-  const size_t need = 10 * A + 256 + tmpb;
-  otsdb_status rc = ensure(&c->rows_ws, &c->rows_ws_cap, need);
-  if (rc) return rc;
-  char* w = (char*)c->rows_ws;
-  int64_t* series_row = (int64_t*)w;
-  uint8_t* slow = (uint8_t*)(w + A);
-  int64_t* arena_sz = (int64_t*)(w + 2 * A);
-  int64_t* arena_off = (int64_t*)(w + 3 * A);
-  int64_t* o_rows = (int64_t*)(w + 4 * A);
-  int64_t* o_q = (int64_t*)(w + 5 * A);
-  int64_t* o_v = (int64_t*)(w + 6 * A);
-  int64_t* row_off = (int64_t*)(w + 7 * A);
-  int64_t* q_off = (int64_t*)(w + 8 * A);
-  int64_t* v_off = (int64_t*)(w + 9 * A);
-  int* err = (int*)(w + 10 * A);
-  void* tmp = w + 10 * A + 256;
-  HIP_TRY(hipMemsetAsync(err, 0, 4, st));
-  for (int64_t* a : {arena_sz, o_rows, o_q, o_v})
-    HIP_TRY(hipMemsetAsync(a + S, 0, 8, st));
-  hipLaunchKernelGGL(k_series_rows, dim3(blocks_for(R + 1, 256)), dim3(256), 0,
-                     st, R, S, in->row_series, series_row);
-  if (S > 0)
-    hipLaunchKernelGGL(k_span_plan, dim3(blocks_for(S, 4)), dim3(256), 0, st, C,
-                       S, (const int64_t*)series_row, slow, arena_sz, o_rows,
-                       o_q, o_v, err);
-  HIP_TRY(hipGetLastError());
-  if ((rc = scan_excl(tmp, tmpb, arena_sz, arena_off, S, st))) return rc;
-  HIP_TRY(hipMemcpyAsync(&c->h_small[0], arena_off + S, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(&c->h_small[1], err, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if ((int)(c->h_small[1] & 0xFFFFFFFF))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "a row without a data point");
-  const int64_t arena = c->h_small[0];
-  *identity = arena == 0;
-  if (arena > 0) {
-    rc = ensure(&c->rows_scr, &c->rows_scr_cap, (size_t)arena + 256);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_span_replay, dim3((unsigned)S), dim3(64), 0, st, C, S,
-                       (const int64_t*)series_row, (const uint8_t*)slow,
-                       (const int64_t*)arena_off, (uint8_t*)c->rows_scr, o_rows,
-                       o_q, o_v);
-    HIP_TRY(hipGetLastError());
-  }
-  if ((rc = scan_excl(tmp, tmpb, o_rows, row_off, S, st))) return rc;
-  if ((rc = scan_excl(tmp, tmpb, o_q, q_off, S, st))) return rc;
-  if ((rc = scan_excl(tmp, tmpb, o_v, v_off, S, st))) return rc;
-  HIP_TRY(hipMemcpyAsync(&c->h_small[2], row_off + S, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(&c->h_small[3], q_off + S, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(&c->h_small[4], v_off + S, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  *n_out = c->h_small[2];
-  if (qbytes) *qbytes = c->h_small[3];
-  if (vbytes) *vbytes = c->h_small[4];
-  if (own >= 0) {
-    if (*identity) return OTSDB_OK;  // the input is the span order
-    if ((rc = cells_buffer(c, own, *n_out, c->h_small[3], c->h_small[4], owned)))
-      return rc;
-    o = owned;
-    qcap = c->h_small[3];
-    vcap = c->h_small[4];
-  }
-  if (!o) return OTSDB_OK;
-  if (c->h_small[3] > qcap || c->h_small[4] > vcap)
-    return fail(OTSDB_E_CAPACITY, "span output capacity");
-  if (S > 0)
-    hipLaunchKernelGGL(k_span_write, dim3(blocks_for(S, 4)), dim3(256), 0, st,
-                       C, S, (const int64_t*)series_row, (const uint8_t*)slow,
-                       (const int64_t*)arena_off, (const uint8_t*)c->rows_scr,
-                       (const int64_t*)row_off, (const int64_t*)q_off,
-                       (const int64_t*)v_off, o->row_series, o->row_base_s,
-                       o->qual_off, o->qual, o->val_off, o->val);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(o->qual_off + *n_out, q_off + S, 8,
-                         hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(o->val_off + *n_out, v_off + S, 8,
-                         hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return OTSDB_OK;
-}
-
-// a context-owned cells buffer for R rows, qb / vb bytes
-otsdb_status cells_buffer(otsdb_ctx* c, int which, int64_t R, int64_t qb,
-                          int64_t vb, otsdb_cells_out* o) {
-  const size_t a = ((size_t)(R + 1) * 8 + 255) & ~(size_t)255;
-  const size_t q = ((size_t)qb + 256) & ~(size_t)255;
-  const size_t v = ((size_t)vb + 256) & ~(size_t)255;
-  otsdb_status rc =
-      ensure(&c->raw_cells[which], &c->raw_cells_cap[which], 4 * a + q + v);
-  if (rc) return rc;
-  char* p = (char*)c->raw_cells[which];
-  o->row_series = (int64_t*)p;
-  o->row_base_s = (int64_t*)(p + a);
-  o->qual_off = (int64_t*)(p + 2 * a);
-  o->val_off = (int64_t*)(p + 3 * a);
-  o->qual = (uint8_t*)(p + 4 * a);
-  o->val = (uint8_t*)(p + 4 * a + q);
-  return OTSDB_OK;
-}
-
-// The storage rows taken verbatim, when they can be: every row one
-// compacted column (k_rows_shape), the rows of each series in base-time
-// order, every series in one group — the rows ARE the compacted, assembled
-// spans, viewed in place (qual_off / val_off point into the column offsets).
-// The cells fold checks the rest as it streams (Params.check_order).
-// Flags spec_miss when the view does not hold or the query would not
-// stream every point through the cells fold; the caller then compacts.
-otsdb_status spec_miss(otsdb_ctx* c) {
-  c->spec_miss = true;
-  return OTSDB_E_UNSUPPORTED;
-}
-
-otsdb_status run_raw_verbatim(otsdb_ctx* c, const otsdb_query_spec* spec,
-                              const otsdb_raw_rows* raw, const otsdb_batch* b,
-                              otsdb_result* out, std::vector<int64_t>& goff) {
-  hipStream_t st = c->stream;
-  const int64_t R = raw->n_rows;
-  if (R <= 0 || goff.empty() || goff.back() != b->n_series ||
-      !(spec->ds_interval_ms > 0) || spec->run_all || anchored(spec))
-    return spec_miss(c);
-  RawDev D{R, raw->row_col_off, raw->col_qual_off, raw->qual, raw->col_val_off,
-           raw->val, raw->col_ts};
-  int* bad = (int*)c->d_mm;
-  HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), st));
-  hipLaunchKernelGGL(k_rows_shape, dim3(blocks_for(R, 256)), dim3(256), 0, st,
-                     D, raw->row_series, raw->row_base_s, bad);
-  HIP_TRY(hipGetLastError());
-  int h[3] = {0, 0, 0};
-  int64_t c0 = 0;
-  HIP_TRY(hipMemcpyAsync(h, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(&c0, raw->row_col_off, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (h[0]) return spec_miss(c);
-  const otsdb_cells cc{R, raw->row_series, raw->row_base_s,
-                       raw->col_qual_off + c0, raw->qual,
-                       raw->col_val_off + c0, raw->val};
-  c->verbatim = true;
-  const otsdb_status rc = run_cells_impl(c, spec, &cc, b, out, goff);
-  c->verbatim = false;
+// what no partials entry takes: the grid of a query the ranks cannot merge
+otsdb_status partials_grid(otsdb_ctx* c, const otsdb_query_spec* spec,
+                           const otsdb_batch* b, Params* P) {
+  otsdb_status rc = check_spec(spec);
+  if (!rc) rc = make_params(spec, P, c);
+  if (!rc && !(spec->ds_interval_ms > 0 || spec->run_all))
+    rc = fail(OTSDB_E_UNSUPPORTED,
+              "raw group-by across ranks (union timestamps need an all-gather)");
+  if (!rc && !P->run_all && !P->fill &&
+      (double)b->n_series * (double)P->nb > 4.0e9)
+    rc = fail(OTSDB_E_UNSUPPORTED, "grid trimming is not supported across ranks");
   return rc;
 }
 
-// The query from storage rows: compaction -> span assembly -> the cells
-// query (DEVICE pointers).
-otsdb_status run_raw_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                          const otsdb_raw_rows* raw, int fix,
-                          const otsdb_batch* b, otsdb_result* out,
-                          std::vector<int64_t>& goff) {
-  hipStream_t st = c->stream;
-  if (!raw->row_series) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null row_series");
-  if (!raw->row_base_s || !raw->row_col_off || !raw->col_qual_off ||
-      !raw->col_val_off || (raw->n_rows > 0 && (!raw->qual || !raw->val)))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null raw row array");
-  {
-    c->spec_miss = false;
-    const otsdb_status v = run_raw_verbatim(c, spec, raw, b, out, goff);
-    if (!c->spec_miss) return v;
-    c->spec_miss = false;
-  }
-  int64_t nk = 0, tq = 0, tv = 0;
-  otsdb_cells_out co;
-  otsdb_status rc;
-  {
-    StageTimer tm(c, 5);  // query-time compaction
-    rc = compact_impl(c, raw, fix, nullptr, 0, 0, &nk, &tq, &tv, st, 0, &co);
-  }
-  if (rc) return rc;
-  otsdb_cells cc{nk, co.row_series, co.row_base_s, co.qual_off, co.qual,
-                 co.val_off, co.val};
-  int64_t ns = 0, sq = 0, sv = 0;
-  bool identity = true;
-  otsdb_cells_out so;
-  {
-    StageTimer tm(c, 6);  // span assembly
-    rc = span_impl(c, &cc, b->n_series, nullptr, 0, 0, &ns, &sq, &sv,
-                   &identity, st, 1, &so);
-  }
-  if (rc) return rc;
-  if (!identity)
-    cc = otsdb_cells{ns, so.row_series, so.row_base_s, so.qual_off, so.qual,
-                     so.val_off, so.val};
-  return run_cells_impl(c, spec, &cc, b, out, goff);
-}
-
-// ------------------------------------------------------ histogram queries
-// (otsdb_hist_*, hist.hip)
-
-// Float.compare (HistogramBucket.compareTo's order): -0.0 below 0.0, NaN
-// above everything and equal to itself
-int float_compare(float a, float b) {
-  if (a < b) return -1;
-  if (a > b) return 1;
-  auto bits = [](float f) {
-    int32_t i;
-    memcpy(&i, &f, 4);
-    return f != f ? (int32_t)0x7fc00000 : i;  // floatToIntBits
-  };
-  const int32_t ia = bits(a), ib = bits(b);
-  return ia == ib ? 0 : (ia < ib ? -1 : 1);
-}
-
-// the argument checks of every histogram entry and the grid: no device work
-otsdb_status hist_check(const otsdb_query_spec* s, const otsdb_hist_columns* h,
-                        int32_t n_pct, Params* P) {
-  if (h->n_bins < 1)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "histogram schema of %d buckets",
-                h->n_bins);
-  if (h->n_bins + 2 > kHistMaxRow)
-    return fail(OTSDB_E_UNSUPPORTED,
-                "histogram rows of %d counts (the limit is %d)", h->n_bins + 2,
-                kHistMaxRow);
-  if (n_pct < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "n_pct < 0");
-  if (n_pct > kHistMaxPct)
-    return fail(OTSDB_E_UNSUPPORTED, "%d percentiles (the limit is %d)", n_pct,
-                kHistMaxPct);
-  if (!h->lower || !h->upper)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "no histogram bucket schema");
-  for (int k = 1; k < h->n_bins; ++k) {
-    int cmp = float_compare(h->lower[k - 1], h->lower[k]);
-    if (!cmp) cmp = float_compare(h->upper[k - 1], h->upper[k]);
-    if (cmp >= 0)
-      return fail(OTSDB_E_ILLEGAL_ARGUMENT,
-                  "histogram buckets must ascend strictly (index %d)", k);
-  }
-  if (s->run_all)
-    return fail(OTSDB_E_UNSUPPORTED, "histogram queries with 0all");
-  if (s->use_calendar)
-    return fail(OTSDB_E_UNSUPPORTED,
-                "histogram queries over calendar intervals");
-  if (s->ds_interval_ms == 0)
-    return fail(OTSDB_E_UNSUPPORTED, "histogram queries without a downsampler");
-  if (s->ds_interval_ms < 0)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative interval");
-  if (s->start_ms < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative start");
-  // the grid of the NONE-fill downsampler: every bucket start <= end_ms from
-  // align(start + interval - 1) on; nothing else of the spec is read
-  otsdb_query_spec g = *s;
-  g.agg_id = OTSDB_AGG_SUM;
-  g.ds_agg_id = OTSDB_AGG_SUM;
-  g.interp = OTSDB_INTERP_DEFAULT;
-  g.fill = OTSDB_FILL_NONE;
-  g.rate = g.counter = g.drop_resets = 0;
-  const otsdb_status rc = make_params(&g, P);
-  if (rc) return rc;
-  if (P->nb > 0 && P->gbase == 0)
-    return fail(OTSDB_E_UNSUPPORTED,
-                "a histogram bucket at timestamp 0 (the reference's end mark)");
-  return OTSDB_OK;
-}
-
-otsdb_status hist_dense_budget(int64_t G, int64_t nb, int R) {
-  if ((double)G * (double)nb * (double)R * 8.0 > (double)kHistDenseBudget)
-    return fail(OTSDB_E_CAPACITY,
-                "dense histogram sums of %lld groups x %lld buckets x %d counts "
-                "pass %lld bytes", (long long)G, (long long)nb, R,
-                (long long)kHistDenseBudget);
-  return OTSDB_OK;
-}
-
-// tiles of at most kHistTile members; a group of several tiles gets one
-// partial slot per tile (consecutive, in member order)
-struct HistTiles {
-  std::vector<int64_t> g, m0, m1, slot, mg_g, mg_s0, mg_s1;
-  int64_t n_slots = 0;
-};
-
-void hist_tiles(const std::vector<int64_t>& goff, HistTiles* T) {
-  for (size_t g = 0; g + 1 < goff.size(); ++g) {
-    const int64_t a = goff[g], e = goff[g + 1];
-    if (e <= a) continue;
-    const bool whole = e - a <= kHistTile;
-    if (!whole) {
-      T->mg_g.push_back((int64_t)g);
-      T->mg_s0.push_back(T->n_slots);
+// one aggregator's partials (the context locked, the stream bound)
+otsdb_status partials_locked(otsdb_ctx* c, const otsdb_query_spec* spec,
+                             const otsdb_batch* b, std::vector<int64_t>& goff,
+                             const otsdb_partial* init,
+                             const uint8_t* init_emit, otsdb_partial* partials,
+                             uint8_t* emit) {
+  Params P;
+  otsdb_status rc = partials_grid(c, spec, b, &P);
+  if (!rc) {
+    const BatchDev B = batch_dev(b);
+    Work W;
+    const int64_t G = (int64_t)goff.size() - 1;
+    if (G * P.nb > 0 && init) {
+      // groups with no member here pass their state on unchanged
+      if (init != partials)
+        HIP_TRY(hipMemcpyAsync(partials, init,
+                               sizeof(otsdb_partial) * (size_t)G * P.nb,
+                               hipMemcpyDeviceToDevice, c->stream));
+      if (init_emit != emit)
+        HIP_TRY(hipMemcpyAsync(emit, init_emit, (size_t)G * P.nb,
+                               hipMemcpyDeviceToDevice, c->stream));
+    } else if (G * P.nb > 0) {
+      hipMemsetAsync(emit, 0, (size_t)G * P.nb, c->stream);
+      hipMemsetAsync(partials, 0, sizeof(otsdb_partial) * (size_t)G * P.nb,
+                     c->stream);
     }
-    for (int64_t m = a; m < e; m += kHistTile) {
-      T->g.push_back((int64_t)g);
-      T->m0.push_back(m);
-      T->m1.push_back(std::min(m + kHistTile, e));
-      T->slot.push_back(whole ? -1 : T->n_slots++);
-    }
-    if (!whole) T->mg_s1.push_back(T->n_slots);
+    rc = run_pipeline(c, spec, B, b->group_members, goff, P, W, 1,
+                      (Packed*)partials, emit, nullptr, nullptr,
+                      (const Packed*)init, init_emit);
+    int err = 0;
+    if (!rc) rc = read_err(c, &err);
+    if (!rc && (err & ERR_RATE_TS)) rc = rate_ts_error();
   }
-}
-
-// the tiles' partials take the dense array's byte budget too (checked before
-// the workspace is sized)
-otsdb_status hist_partial_budget(const HistTiles& T, int64_t nb, int R) {
-  if ((double)T.n_slots * (double)nb * (double)R * 8.0 > (double)kHistDenseBudget)
-    return fail(OTSDB_E_CAPACITY,
-                "partial histogram sums of %lld tiles x %lld buckets x %d "
-                "counts pass %lld bytes", (long long)T.n_slots, (long long)nb,
-                R, (long long)kHistDenseBudget);
-  return OTSDB_OK;
-}
-
-// device buffers of one histogram call, carved from the context workspace
-struct HistWork {
-  int64_t *lo, *hi, *tiles, *partial, *dense, *cnt;
-  uint8_t *part_emit, *emit;
-  float* schema;
-  double* dense_pct;
-};
-
-size_t hist_carve(char* base, HistWork* W, int64_t S, const HistTiles* T,
-                  int64_t G, int64_t nb, int R, int n_pct, bool own_dense) {
-  Carve cv{base};
-  const size_t nt = T ? T->g.size() * 4 + T->mg_g.size() * 3 : 0;
-  W->lo = cv.take<int64_t>(S + 1);
-  W->hi = cv.take<int64_t>(S + 1);
-  W->tiles = cv.take<int64_t>(nt + 1);
-  W->partial = cv.take<int64_t>((size_t)(T ? T->n_slots : 0) * nb * R + 2);
-  W->part_emit = cv.take<uint8_t>((size_t)(T ? T->n_slots : 0) * nb + 16);
-  W->dense = cv.take<int64_t>(own_dense ? (size_t)G * nb * R + 2 : 2);
-  W->emit = cv.take<uint8_t>(own_dense ? (size_t)G * nb + 16 : 16);
-  W->schema = cv.take<float>(2 * (size_t)R);
-  W->dense_pct = cv.take<double>((size_t)n_pct * G * nb + 1);
-  W->cnt = cv.take<int64_t>(G + 1);
-  return cv.off + 256;
-}
-
-// the local shard's dense sums: prep, fold, combine.  Every cell of dense /
-// emit is written.  T's arrays stay alive until the caller synchronises.
-otsdb_status hist_partials(otsdb_ctx* c, const otsdb_query_spec* spec,
-                           const Params& P, const otsdb_batch* b,
-                           const otsdb_hist_columns* h, const HistTiles& T,
-                           const HistWork& W, std::vector<int64_t>& tbuf,
-                           int64_t* dense, uint8_t* emit) {
-  hipStream_t st = c->stream;
-  const int64_t S = b->n_series, G = b->n_groups, nb = P.nb;
-  const int R = h->n_bins + 2;
-  c->n_hist_fold = 0;
-  if (G == 0 || nb == 0) return OTSDB_OK;
-  HIP_TRY(hipMemsetAsync(dense, 0, (size_t)G * nb * R * 8, st));
-  HIP_TRY(hipMemsetAsync(emit, 0, (size_t)G * nb, st));
-  const int64_t nt = (int64_t)T.g.size(), nmg = (int64_t)T.mg_g.size();
-  if (nt == 0 || S == 0) return OTSDB_OK;
-  // (a batch without points may come without point columns: none is read)
-  if (!b->offsets || !b->group_members ||
-      (b->n_points > 0 && (!b->ts_ms || !h->counts)))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null batch column");
-  if (((uintptr_t)h->counts) & 7)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "histogram counts not 8-byte aligned");
-  const int Wb = hist_window(R);
-  const int64_t NW = (nb + Wb - 1) / Wb;
-  if ((double)nt * (double)NW >= 2147483647.0)
-    return fail(OTSDB_E_CAPACITY, "histogram fold of %lld tiles x %lld windows",
-                (long long)nt, (long long)NW);
-  // tile table: g | m0 | m1 | slot [nt], then mg_g | mg_s0 | mg_s1 [nmg]
-  tbuf.clear();
-  for (auto* v : {&T.g, &T.m0, &T.m1, &T.slot, &T.mg_g, &T.mg_s0, &T.mg_s1})
-    tbuf.insert(tbuf.end(), v->begin(), v->end());
-  HIP_TRY(hipMemcpyAsync(W.tiles, tbuf.data(), tbuf.size() * 8,
-                         hipMemcpyHostToDevice, st));
-  const int64_t* d_g = W.tiles;
-  const int64_t* d_m0 = d_g + nt;
-  const int64_t* d_m1 = d_m0 + nt;
-  const int64_t* d_slot = d_m1 + nt;
-  const int64_t* d_mg = d_slot + nt;
-  {
-    StageTimer tm(c, 8);
-    hipLaunchKernelGGL(k_hist_prep, dim3(blocks_for(S, 256)), dim3(256), 0, st,
-                       P, S, b->offsets, b->ts_ms, W.lo, W.hi);
-    const int first_only = spec->ds_agg_id != OTSDB_AGG_SUM;
-    const bool vec = (R % 2 == 0) && (((uintptr_t)h->counts) & 15) == 0;
-    const int lds = hist_lds_bytes(R, (int)std::min<int64_t>(Wb, nb));
-    const dim3 grid((unsigned)(nt * NW)), blk(HIST_THREADS);
-    auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, grid, blk, lds, st, P, b->ts_ms, h->counts, R, Wb,
-                         first_only, (const int64_t*)W.lo, (const int64_t*)W.hi,
-                         nt, d_g, d_m0, d_m1, d_slot, b->group_members, dense,
-                         emit, W.partial, W.part_emit);
-    };
-    if (R <= 128) {
-      if (vec) launch(k_hist_fold<1, true>);
-      else launch(k_hist_fold<1, false>);
-    } else {
-      if (vec) launch(k_hist_fold<2, true>);
-      else launch(k_hist_fold<2, false>);
-    }
-    c->n_hist_fold = 1;
-  }
-  HIP_TRY(hipGetLastError());
-  if (nmg > 0) {
-    StageTimer tm(c, 9);
-    for (int64_t k0 = 0; k0 < nmg; k0 += 65535) {
-      const int64_t n = std::min<int64_t>(65535, nmg - k0);
-      hipLaunchKernelGGL(k_hist_combine,
-                         dim3(blocks_for(nb * R, 256), (unsigned)n), dim3(256),
-                         0, st, nb, R, d_mg + k0, d_mg + nmg + k0,
-                         d_mg + 2 * nmg + k0, (const int64_t*)W.partial,
-                         (const uint8_t*)W.part_emit, dense, emit);
-    }
-    HIP_TRY(hipGetLastError());
-  }
-  return OTSDB_OK;
-}
-
-// percentiles and the compacted result from dense sums; synchronises
-otsdb_status hist_finalize(otsdb_ctx* c, const Params& P, int64_t G,
-                           const otsdb_hist_columns* h, const HistWork& W,
-                           const int64_t* dense, const uint8_t* emit,
-                           const float* pcts, int n_pct,
-                           otsdb_hist_result* out, int64_t* total) {
-  hipStream_t st = c->stream;
-  const int64_t nb = P.nb;
-  const int K = h->n_bins, R = K + 2;
-  c->n_hist_pct = 0;
-  *total = 0;
-  if (G == 0 || nb == 0) {
-    HIP_TRY(hipMemsetAsync(out->offsets, 0, sizeof(int64_t) * (G + 1), st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return OTSDB_OK;
-  }
-  const int64_t cells = G * nb;
-  if (n_pct > 0) {
-    HIP_TRY(hipMemcpyAsync(W.schema, h->lower, 4 * (size_t)K,
-                           hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(W.schema + R, h->upper, 4 * (size_t)K,
-                           hipMemcpyHostToDevice, st));
-    HistPct hp;
-    for (int q = 0; q < kHistMaxPct; ++q)
-      hp.p[q] = q < n_pct ? (double)pcts[q] : 0.0;  // float widened
-    StageTimer tm(c, 10);
-    const dim3 grid(blocks_for(cells, 4)), blk(256);
-    auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, grid, blk, 0, st, cells, R, K, dense, emit,
-                         (const float*)W.schema, (const float*)(W.schema + R),
-                         hp, n_pct, W.dense_pct);
-    };
-    switch ((K + 63) / 64) {
-      case 1: launch(k_hist_percentiles<1>); break;
-      case 2: launch(k_hist_percentiles<2>); break;
-      case 3: launch(k_hist_percentiles<3>); break;
-      default: launch(k_hist_percentiles<4>); break;
-    }
-    c->n_hist_pct = 1;
-    HIP_TRY(hipGetLastError());
-  }
-  {
-    StageTimer tm(c, 11);
-    hipLaunchKernelGGL(k_hist_count, dim3(blocks_for(G, 4)), dim3(256), 0, st,
-                       G, nb, emit, W.cnt);
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, G,
-                       (const int64_t*)W.cnt, out->offsets);
-    hipLaunchKernelGGL(k_hist_scatter, dim3(blocks_for(G, 4)), dim3(256), 0, st,
-                       P, G, R, n_pct, emit, (const int64_t*)out->offsets,
-                       out->capacity, dense, (const double*)W.dense_pct, out->ts,
-                       out->pct_val, out->counts);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipMemcpyAsync(&c->h_small[1], out->offsets + G, sizeof(int64_t),
-                         hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  *total = c->h_small[1];
-  if (*total > out->capacity) {
-    c->result_short = true;
-    return fail(OTSDB_E_CAPACITY, "result capacity %lld < %lld points",
-                (long long)out->capacity, (long long)*total);
-  }
-  return OTSDB_OK;
-}
-
-otsdb_status hist_out_check(const otsdb_hist_result* out, int32_t n_pct) {
-  if (n_pct == 0 && !out->counts)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT,
-                "no percentile and no counts output asked for");
-  if (out->capacity < 0 || !out->offsets || (out->capacity > 0 && !out->ts) ||
-      (n_pct > 0 && out->capacity > 0 && !out->pct_val))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null result array");
-  return OTSDB_OK;
-}
-
-// the whole query on device pointers (the context locked, the stream bound)
-otsdb_status hist_run_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                           const Params& P, const otsdb_batch* b,
-                           const otsdb_hist_columns* h,
-                           const std::vector<int64_t>& goff, const float* pcts,
-                           int n_pct, otsdb_hist_result* out, int64_t* total) {
-  const int R = h->n_bins + 2;
-  HistTiles T;
-  hist_tiles(goff, &T);
-  otsdb_status rc = hist_partial_budget(T, P.nb, R);
-  if (rc) return rc;
-  HistWork W;
-  const size_t need =
-      hist_carve(nullptr, &W, b->n_series, &T, b->n_groups, P.nb, R, n_pct, true);
-  rc = ensure(&c->ws, &c->ws_cap, need);
-  if (rc) return rc;
-  hist_carve((char*)c->ws, &W, b->n_series, &T, b->n_groups, P.nb, R, n_pct,
-             true);
-  std::vector<int64_t> tbuf;
-  rc = hist_partials(c, spec, P, b, h, T, W, tbuf, W.dense, W.emit);
-  if (!rc)
-    rc = hist_finalize(c, P, b->n_groups, h, W, W.dense, W.emit, pcts, n_pct,
-                       out, total);
-  else
-    hipStreamSynchronize(c->stream);
   return rc;
+}
+
+otsdb_status partials_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
+                           const otsdb_batch* b, const otsdb_partial* init,
+                           const uint8_t* init_emit, otsdb_partial* partials,
+                           uint8_t* emit, void* hip_stream) {
+  if (!c || !spec || !b || !partials || !emit || (!init != !init_emit))
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  DeviceCall dc(c, b, hip_stream);
+  return dc.rc ? dc.rc
+               : partials_locked(c, spec, b, dc.goff, init, init_emit, partials,
+                                 emit);
+}
+
+// the multi_request checks of the entries that exchange partials: the
+// selections take the otsdb_sel_* protocol
+otsdb_status check_multi_partials(const otsdb_query_spec* spec,
+                                  const Req& q) {
+  const otsdb_status rc = check_req(spec, q);
+  if (rc) return rc;
+  for (int i = 0; i < q.n; ++i)
+    if (is_selection(q.aggs[i]))
+      return fail(OTSDB_E_ILLEGAL_ARGUMENT,
+                  "percentiles across ranks: use the otsdb_sel_* protocol "
+                  "(otsdb_sel_retarget for several)");
+  return OTSDB_OK;
+}
+
+// the protocol's device words, after the error word (d_err + 128 .. 160):
+// per-pass flags, the scans' "broken" mark
+uint32_t* xs_flags(otsdb_ctx* c) { return (uint32_t*)((char*)c->d_err + 128); }
+uint32_t* xs_broken(otsdb_ctx* c) { return (uint32_t*)((char*)c->d_err + 152); }
+
+int64_t* xs_bnd(otsdb_ctx* c) { return (int64_t*)c->sel.segmem.p; }
+int64_t* xs_off(otsdb_ctx* c) {
+  return (int64_t*)c->sel.segmem.p + (c->sel.G * c->sel.NB + 1);
+}
+uint32_t* xs_segfill(otsdb_ctx* c) {
+  return (uint32_t*)(xs_off(c) + (c->sel.G * c->sel.NB + 1));
+}
+void* xs_scan_tmp(otsdb_ctx* c) {
+  const int64_t GB = c->sel.G * c->sel.NB;
+  return (char*)c->sel.segmem.p + (((size_t)(GB + 1) * 16 + (size_t)GB * 4 + 255) & ~(size_t)255);
+}
+
+XPool xs_pool(otsdb_ctx* c) {
+  auto& S = c->sel;
+  XPool p;
+  p.key = (uint64_t*)S.pool.p;
+  p.seg = S.pool.p ? (int64_t*)((char*)S.pool.p + (size_t)S.pool_cap * 8) : nullptr;
+  p.off = xs_off(c);
+  p.fill = xs_segfill(c);
+  p.cap = S.pool_cap;
+  p.flags = xs_broken(c);
+  return p;
 }
 
 }  // namespace
+
+// ------------------- the query implementations other units call (engine_int.h)
+namespace otsdb {
+namespace eng {
+
+// Grid of buckets every series row is laid out on.
+otsdb_status make_params(const otsdb_query_spec* s, Params* P,
+                         otsdb_ctx* c) {
+  memset(P, 0, sizeof(*P));
+  P->start_ms = s->start_ms;
+  P->end_ms = s->end_ms;
+  P->run_all = s->run_all;
+  P->fill = s->run_all ? 0 : s->fill;
+  P->rate = s->rate;
+  P->counter = s->counter;
+  P->drop_resets = s->drop_resets;
+  P->counter_max = s->counter_max;
+  P->reset_value = s->reset_value;
+  agg_params(P, s->agg_id, s->interp);
+  P->fill_value = (P->fill == OTSDB_FILL_ZERO) ? 0.0 : NAN;
+  if (!(s->ds_interval_ms > 0 || s->run_all)) return OTSDB_OK;  // raw
+  if (is_selection(s->ds_agg_id)) {
+    P->ds_sel = s->ds_agg_id == OTSDB_AGG_MEDIAN ? 1 : 2;
+    P->ds_pct = s->ds_agg_id >= OTSDB_AGG_P999 ? pct_of(s->ds_agg_id) : 0.0;
+  }
+  P->rate_origin_ts = 0;
+  P->rate_origin_val = 0.0;
+  if (s->run_all) {
+    // Downsampler "all": one point at query_start holding the points of
+    // [query_start, query_end) after seek(start) (Downsampler.java:354-379)
+    P->interval = 1;
+    P->inv_interval = 1.0;
+    P->gbase = s->query_start_ms;
+    P->out_ts0 = s->query_start_ms;
+    P->seek_ts = std::max(s->start_ms, s->query_start_ms);
+    P->stop_ts = s->query_end_ms;
+    P->nb = (s->query_start_ms >= s->start_ms &&
+             s->query_start_ms <= s->end_ms) ? 1 : 0;
+    P->narrow = 1;  // every point is bucket 0
+    return OTSDB_OK;
+  }
+  const int64_t iv = s->ds_interval_ms;
+  P->interval = iv;
+  P->inv_interval = 1.0 / (double)iv;
+  if (s->use_calendar && s->n_cal_anchors > 0)  // callers derive stage B
+    return fail(OTSDB_E_UNSUPPORTED,
+                "per-series calendar grids on this entry point");
+  if (s->use_calendar) return make_cal_params(s, P, c);
+  const int64_t grid0 = align_down(s->start_ms + iv - 1, iv);
+  P->gbase = grid0;
+  P->seek_ts = grid0;
+  if (P->fill) {
+    // FillingDownsampler: every bucket of [align(start), align(end)); the
+    // aggregation iterator skips those before start (FillingDownsampler.java
+    // :136-142, AggregationIterator.java:425-447)
+    const int64_t aend = align_down(s->end_ms, iv);
+    P->nb = aend > grid0 ? (aend - grid0) / iv : 0;
+    P->stop_ts = grid0 + P->nb * iv;
+    const int64_t astart = align_down(s->start_ms, iv);
+    if (astart < grid0) {
+      P->rate_origin_ts = astart;
+      P->rate_origin_val = P->fill_value;
+    }
+  } else {
+    P->nb = s->end_ms >= grid0 ? (s->end_ms - grid0) / iv + 1 : 0;
+    P->stop_ts = grid0 + P->nb * iv;
+  }
+  // points fed to the bucket fold lie in [gbase, stop_ts): 32-bit offsets
+  P->narrow = iv < (int64_t(1) << 31) && P->nb < (int64_t(1) << 32) / iv;
+  return OTSDB_OK;
+}
+
+otsdb_status run_device_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
+                             const otsdb_batch* b, otsdb_result* out,
+                             std::vector<int64_t>& goff) {
+  otsdb_status rc = check_spec(spec);
+  if (rc) return rc;
+  if (anchored(spec)) return run_anchored(c, spec, b, out, goff);
+  Params P;
+  rc = make_params(spec, &P, c);
+  if (rc) return rc;
+  if (misaligned(b))
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT,
+                "ts_ms/val must be 16-byte aligned (16-B streaming loads)");
+  const BatchDev B = batch_dev(b);
+  if (!(spec->ds_interval_ms > 0 || spec->run_all))
+    return run_raw(c, spec, b, B, goff, P, out);
+  Work W;
+  rc = run_pipeline(c, spec, B, b->group_members, goff, P, W, 0, nullptr,
+                    nullptr);
+  if (rc) return rc;
+  const int64_t G = (int64_t)goff.size() - 1;
+  rc = compact(c, P, G, W.out_val, W.out_emit, W.counts, out);
+  if (rc) return rc;
+  return finish(c, G, out);
+}
+
+// ------------------------------------------------------- rollup queries
+// otsdb_agg_run_rollup*: the points are a rollup table's cells; R (the
+// rollup aggregator) and the downsampling function F pick how a bucket is
+// computed (Downsampler.java:162-228, FillingDownsampler.java:196-252;
+// DESIGN.md §4.3).
+
+// The checks that need no device, and the state the rows are built with
+// (ROLLUP_NONE: the ordinary F.runDouble — the single query, counts ignored).
+otsdb_status check_rollup(const otsdb_query_spec* s, const Rollup& r,
+                          RollupKind* kind) {
+  if (r.agg < 0 || r.agg >= OTSDB_AGG_COUNT_IDS)
+    return fail(OTSDB_E_NO_SUCH_ELEMENT, "No such aggregator: %d", r.agg);
+  otsdb_status rc = check_spec(s);
+  if (rc) return rc;
+  if (r.agg == OTSDB_AGG_DEV)
+    return fail(OTSDB_E_UNSUPPORTED,
+                "standard deviation over rolled up data is not supported");
+  if (!(s->ds_interval_ms > 0 || s->run_all))
+    return fail(OTSDB_E_UNSUPPORTED, "a rollup query without a downsampler");
+  if (s->n_cal_anchors > 0)
+    return fail(OTSDB_E_UNSUPPORTED,
+                "rollup queries over per-series calendar anchors");
+  *kind = ROLLUP_NONE;
+  if (r.agg == OTSDB_AGG_AVG) {
+    if (s->ds_agg_id != OTSDB_AGG_AVG)
+      return fail(OTSDB_E_UNSUPPORTED,
+                  "rollup avg downsampled with another function");
+    if (!r.cnt)
+      return fail(OTSDB_E_ILLEGAL_ARGUMENT, "rollup avg needs value_count");
+    *kind = ROLLUP_AVG;
+  } else if (s->ds_agg_id == OTSDB_AGG_COUNT) {
+    *kind = ROLLUP_COUNT;
+  }
+  return OTSDB_OK;
+}
+
+// device pointers throughout (r.cnt too)
+otsdb_status run_rollup_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
+                             const otsdb_batch* b, const Rollup& r,
+                             otsdb_result* out, std::vector<int64_t>& goff) {
+  RollupKind kind;
+  otsdb_status rc = check_rollup(spec, r, &kind);
+  if (rc) return rc;
+  if (kind == ROLLUP_AVG && (((uintptr_t)r.cnt) & 15) != 0)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT,
+                "value_count must be 16-byte aligned (16-B streaming loads)");
+  RollupScope scope(c, kind, r.cnt);
+  return run_device_impl(c, spec, b, out, goff);
+}
+
+// Query straight from compacted columns: the fused decode + downsample when
+// the query and the columns allow it, else decode -> columnar -> pipeline.
+// mq: several aggregators (otsdb_agg_run_cells_multi_device; `spec` carries
+// output 0's, `out` is unused): the same routing, with the shared-rows
+// pipeline in place of run_pipeline where the outputs can share them (with
+// OTSDB_SPEC_CELLS_MULTI_FOLD on an eligible request: the cells fold over
+// the envelope state in its place, multi_fold_pass), and run_multi_impl over
+// the decoded columns otherwise (never folded).
+otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
+                            const otsdb_cells* cells, const otsdb_batch* b,
+                            otsdb_result* out, std::vector<int64_t>& goff,
+                            const Req* mq) {
+  otsdb_status rc = check_spec(spec);
+  if (rc) return rc;
+  const int64_t S = b->n_series, R = cells->n_rows;
+  if (S < 0 || R < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
+  const bool ds = spec->ds_interval_ms > 0 || spec->run_all;
+  Params P;
+  // per-series calendar grids rewrite columnar timestamps: decode first
+  const bool fused = ds && !anchored(spec);
+  if (fused) {
+    rc = make_params(spec, &P, c);
+    if (rc) return rc;
+  }
+  if (fused && !P.ds_sel && !P.run_all &&
+      (!mq || multi_shares_rows(spec, *mq, P, S, goff))) {
+    const BatchDev B{S, nullptr, nullptr, nullptr, nullptr, nullptr};
+    Work W;
+    MultiState MS;
+    MultiFoldRun MF;
+    CellsEnd end;
+    // OTSDB_SPEC_CELLS_MULTI_FOLD: the cells fold over the envelope state in
+    // the row pass's place (narrow grids, as the single cells fold; calendar
+    // grids from cells keep the rows)
+    const bool mfold = mq && !c->verbatim && P.narrow &&
+                       multi_folds(spec, *mq, P, OTSDB_SPEC_CELLS_MULTI_FOLD);
+    if (mq) c->n_multi_fold = 0;
+    rc = cells_attempts(
+        c, cells, S, P, &end,
+        [&](const CellsDev& CQ, const int64_t* series_row) {
+          if (mfold)
+            return multi_fold_pass(c, spec, *mq, B, b->group_members, goff, P,
+                                   &CQ, series_row, MF);
+          if (mq) {  // (every attempt its own work set)
+            MS = MultiState();
+            return multi_build(c, spec, *mq, B, b->group_members, goff, P, &CQ,
+                               series_row, MS);
+          }
+          W = Work();
+          return run_pipeline(c, spec, B, b->group_members, goff, P, W, 0,
+                              nullptr, nullptr, &CQ, series_row);
+        },
+        [&]() {
+          if (mfold) return multi_fold_finish(c, *mq, MF);
+          if (mq) return multi_aggregate(c, MS);
+          const int64_t G = (int64_t)goff.size() - 1;
+          const otsdb_status rf =
+              compact(c, P, G, W.out_val, W.out_emit, W.counts, out);
+          return rf ? rf : finish(c, G, out);
+        });
+    if (rc || end != CELLS_DECODE) return rc;
+  }
+  // (verbatim storage rows take only the cells fold)
+  if (c->verbatim) return spec_miss(c);
+  // decode to a columnar batch in the context's own buffer, then the
+  // columnar pipeline (raw group-by, median/percentile or "all" downsampling,
+  // mixed-width columns)
+  otsdb_batch cb;
+  rc = cells_columnar(c, cells, b, &cb);
+  if (rc) return rc;
+  if (mq) return run_multi_impl(c, spec, *mq, &cb, goff, /*may_fold=*/false);
+  return run_device_impl(c, spec, &cb, out, goff);
+}
+
+}  // namespace eng
+}  // namespace otsdb
 
 // =========================================================================
 // C-ABI
@@ -4691,33 +3549,14 @@ void otsdb_ctx_destroy(otsdb_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
-  if (c->ws) hipFree(c->ws);
-  if (c->stage) hipFree(c->stage);
-  if (c->dec_ws) hipFree(c->dec_ws);
-  if (c->ws2) hipFree(c->ws2);
-  if (c->cal) hipFree(c->cal);
-  if (c->acal) hipFree(c->acal);
-  if (c->acal_fill) hipFree(c->acal_fill);
-  if (c->cells_ws) hipFree(c->cells_ws);
-  if (c->cells_col) hipFree(c->cells_col);
-  if (c->rows_ws) hipFree(c->rows_ws);
-  if (c->rows_scr) hipFree(c->rows_scr);
-  if (c->rows_large) hipFree(c->rows_large);
-  for (void* p : c->raw_cells)
-    if (p) hipFree(p);
-  if (c->raw_stage) hipFree(c->raw_stage);
-  if (c->d_tiles) hipFree(c->d_tiles);
-  if (c->sel.pool) hipFree(c->sel.pool);
-  if (c->sel.segmem) hipFree(c->sel.segmem);
-  if (c->cmp_flags) hipFree(c->cmp_flags);
+  for (auto e : c->ev_pool) hipEventDestroy(e);
   if (c->d_err) hipFree(c->d_err);
   if (c->d_merr) hipFree(c->d_merr);
   if (c->h_mdone) hipHostFree(c->h_mdone);
-  for (auto e : c->ev_pool) hipEventDestroy(e);
   if (c->h_small) hipHostFree(c->h_small);
   if (c->h_done) hipHostFree(c->h_done);
   if (c->stream) hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // the device buffers free themselves (DevBuf)
 }
 
 otsdb_status otsdb_agg_lookup(const char* name, int32_t* agg_id) {
@@ -4839,9 +3678,9 @@ static otsdb_status run_host(otsdb_ctx* c, const otsdb_query_spec* spec,
     return std::make_pair(cv.off + 256, p);
   };
   const size_t need = carve(nullptr).first;
-  rc = ensure(&c->stage, &c->stage_cap, need);
+  rc = c->stage.ensure(need);
   if (rc) return rc;
-  auto pp = carve((char*)c->stage).second;
+  auto pp = carve((char*)c->stage.p).second;
   hipStream_t st = c->stream;
   auto h2d = [&](void* d, const void* h, size_t n) -> otsdb_status {
     if (n && h) HIP_TRY(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, st));
@@ -5067,88 +3906,6 @@ otsdb_status otsdb_agg_run_cells_panel_device(
   return dc.rc ? dc.rc : run_cells_panel_impl(c, spec, q, cells, b, dc.goff);
 }
 
-}  // extern "C"
-
-namespace {
-// what no partials entry takes: the grid of a query the ranks cannot merge
-otsdb_status partials_grid(otsdb_ctx* c, const otsdb_query_spec* spec,
-                           const otsdb_batch* b, Params* P) {
-  otsdb_status rc = check_spec(spec);
-  if (!rc) rc = make_params(spec, P, c);
-  if (!rc && !(spec->ds_interval_ms > 0 || spec->run_all))
-    rc = fail(OTSDB_E_UNSUPPORTED,
-              "raw group-by across ranks (union timestamps need an all-gather)");
-  if (!rc && !P->run_all && !P->fill &&
-      (double)b->n_series * (double)P->nb > 4.0e9)
-    rc = fail(OTSDB_E_UNSUPPORTED, "grid trimming is not supported across ranks");
-  return rc;
-}
-
-// one aggregator's partials (the context locked, the stream bound)
-otsdb_status partials_locked(otsdb_ctx* c, const otsdb_query_spec* spec,
-                             const otsdb_batch* b, std::vector<int64_t>& goff,
-                             const otsdb_partial* init,
-                             const uint8_t* init_emit, otsdb_partial* partials,
-                             uint8_t* emit) {
-  Params P;
-  otsdb_status rc = partials_grid(c, spec, b, &P);
-  if (!rc) {
-    const BatchDev B = batch_dev(b);
-    Work W;
-    const int64_t G = (int64_t)goff.size() - 1;
-    if (G * P.nb > 0 && init) {
-      // groups with no member here pass their state on unchanged
-      if (init != partials)
-        HIP_TRY(hipMemcpyAsync(partials, init,
-                               sizeof(otsdb_partial) * (size_t)G * P.nb,
-                               hipMemcpyDeviceToDevice, c->stream));
-      if (init_emit != emit)
-        HIP_TRY(hipMemcpyAsync(emit, init_emit, (size_t)G * P.nb,
-                               hipMemcpyDeviceToDevice, c->stream));
-    } else if (G * P.nb > 0) {
-      hipMemsetAsync(emit, 0, (size_t)G * P.nb, c->stream);
-      hipMemsetAsync(partials, 0, sizeof(otsdb_partial) * (size_t)G * P.nb,
-                     c->stream);
-    }
-    rc = run_pipeline(c, spec, B, b->group_members, goff, P, W, 1,
-                      (Packed*)partials, emit, nullptr, nullptr,
-                      (const Packed*)init, init_emit);
-    int err = 0;
-    if (!rc) rc = read_err(c, &err);
-    if (!rc && (err & ERR_RATE_TS)) rc = rate_ts_error();
-  }
-  return rc;
-}
-
-otsdb_status partials_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
-                           const otsdb_batch* b, const otsdb_partial* init,
-                           const uint8_t* init_emit, otsdb_partial* partials,
-                           uint8_t* emit, void* hip_stream) {
-  if (!c || !spec || !b || !partials || !emit || (!init != !init_emit))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  DeviceCall dc(c, b, hip_stream);
-  return dc.rc ? dc.rc
-               : partials_locked(c, spec, b, dc.goff, init, init_emit, partials,
-                                 emit);
-}
-
-// the multi_request checks of the entries that exchange partials: the
-// selections take the otsdb_sel_* protocol
-otsdb_status check_multi_partials(const otsdb_query_spec* spec,
-                                  const Req& q) {
-  const otsdb_status rc = check_req(spec, q);
-  if (rc) return rc;
-  for (int i = 0; i < q.n; ++i)
-    if (is_selection(q.aggs[i]))
-      return fail(OTSDB_E_ILLEGAL_ARGUMENT,
-                  "percentiles across ranks: use the otsdb_sel_* protocol "
-                  "(otsdb_sel_retarget for several)");
-  return OTSDB_OK;
-}
-}  // namespace
-
-extern "C" {
-
 otsdb_status otsdb_agg_partials_multi_device(
     otsdb_ctx* c, const otsdb_query_spec* spec, int32_t n_out,
     const int32_t* agg_ids, const int32_t* interps, const otsdb_batch* b,
@@ -5242,9 +3999,9 @@ otsdb_status otsdb_agg_finalize_multi_device(
     }
     return cv.off + 256;
   };
-  rc = ensure(&c->ws, &c->ws_cap, carve(nullptr));
+  rc = c->ws.ensure(carve(nullptr));
   if (rc) return rc;
-  carve((char*)c->ws);
+  carve((char*)c->ws.p);
   for (int i = 0; i < q.n; ++i) {
     A.slot[i] = kMultiSlotDev;  // (ordered: dev)
     with_monoid(q.aggs[i], [&](auto tag) {
@@ -5316,9 +4073,9 @@ otsdb_status otsdb_agg_finalize_device(otsdb_ctx* c,
       cnt = cv.take<int64_t>(G + 1);
       return cv.off + 256;
     };
-    rc = ensure(&c->ws, &c->ws_cap, carve(nullptr));
+    rc = c->ws.ensure(carve(nullptr));
     if (!rc) {
-      carve((char*)c->ws);
+      carve((char*)c->ws.p);
       hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream);
       bool ok = true;
       if (GB > 0)
@@ -5439,37 +4196,6 @@ otsdb_status otsdb_sel_retarget(otsdb_ctx* c, int32_t agg_id) {
   return OTSDB_OK;
 }
 
-namespace {
-// the protocol's device words, after the error word (d_err + 128 .. 160):
-// per-pass flags, the scans' "broken" mark
-uint32_t* xs_flags(otsdb_ctx* c) { return (uint32_t*)((char*)c->d_err + 128); }
-uint32_t* xs_broken(otsdb_ctx* c) { return (uint32_t*)((char*)c->d_err + 152); }
-
-int64_t* xs_bnd(otsdb_ctx* c) { return (int64_t*)c->sel.segmem; }
-int64_t* xs_off(otsdb_ctx* c) {
-  return (int64_t*)c->sel.segmem + (c->sel.G * c->sel.NB + 1);
-}
-uint32_t* xs_segfill(otsdb_ctx* c) {
-  return (uint32_t*)(xs_off(c) + (c->sel.G * c->sel.NB + 1));
-}
-void* xs_scan_tmp(otsdb_ctx* c) {
-  const int64_t GB = c->sel.G * c->sel.NB;
-  return (char*)c->sel.segmem + (((size_t)(GB + 1) * 16 + (size_t)GB * 4 + 255) & ~(size_t)255);
-}
-
-XPool xs_pool(otsdb_ctx* c) {
-  auto& S = c->sel;
-  XPool p;
-  p.key = (uint64_t*)S.pool;
-  p.seg = S.pool ? (int64_t*)((char*)S.pool + (size_t)S.pool_cap * 8) : nullptr;
-  p.off = xs_off(c);
-  p.fill = xs_segfill(c);
-  p.cap = S.pool_cap;
-  p.flags = xs_broken(c);
-  return p;
-}
-}  // namespace
-
 otsdb_status otsdb_sel_hist_device(otsdb_ctx* c, int32_t pass,
                                    const int64_t* counts, const uint8_t* emit,
                                    const int64_t* krange, uint32_t* hist_prev,
@@ -5502,7 +4228,7 @@ otsdb_status otsdb_sel_hist_device(otsdb_ctx* c, int32_t pass,
       S.scan_tmp = tmp;
       const size_t need =
           (((size_t)(GB + 1) * 16 + (size_t)GB * 4 + 255) & ~(size_t)255) + tmp;
-      otsdb_status rc = ensure(&S.segmem, &S.segmem_bytes, need);
+      otsdb_status rc = S.segmem.ensure(need);
       if (rc) return rc;
       HIP_TRY(hipMemsetAsync(xs_bnd(c), 0, (size_t)(GB + 1) * 8, st));
       hipLaunchKernelGGL(k_counts_to_dense, dim3(blocks_for(GB, 256)), dim3(256),
@@ -5548,10 +4274,10 @@ otsdb_status otsdb_sel_hist_device(otsdb_ctx* c, int32_t pass,
     int mode = 1;
     if (pass == 1) {  // the candidates: every later pass and the pick read them
       const int64_t cap = bound > 0 ? bound : 1;
-      otsdb_status rc = ensure(&S.pool, &S.pool_bytes, (size_t)cap * 16);
+      otsdb_status rc = S.pool.ensure((size_t)cap * 16);
       if (rc) return rc;
       S.pool_cap = cap;
-      HIP_TRY(hipMemsetAsync((char*)S.pool + (size_t)cap * 8, 0xFF,
+      HIP_TRY(hipMemsetAsync((char*)S.pool.p + (size_t)cap * 8, 0xFF,
                              (size_t)cap * 8, st));  // every slot unfilled
       HIP_TRY(hipMemsetAsync(xs_segfill(c), 0, (size_t)GB * 4, st));
       S.pool_built = true;
@@ -5681,246 +4407,6 @@ otsdb_status otsdb_encode_cells_device(otsdb_ctx* c, const otsdb_batch* b,
   return OTSDB_OK;
 }
 
-otsdb_status otsdb_compact_rows_device(otsdb_ctx* c, const otsdb_raw_rows* raw,
-                                       int32_t fix_duplicates,
-                                       const otsdb_cells_out* out,
-                                       int64_t qual_capacity,
-                                       int64_t val_capacity, int64_t* n_out_rows,
-                                       void* hip_stream) {
-  if (!c || !raw || !n_out_rows) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  return compact_impl(c, raw, fix_duplicates != 0, out, qual_capacity,
-                      val_capacity, n_out_rows, nullptr, nullptr, st);
-}
-
-otsdb_status otsdb_span_assemble_device(otsdb_ctx* c, const otsdb_cells* cells,
-                                        int64_t n_series,
-                                        const otsdb_cells_out* out,
-                                        int64_t qual_capacity,
-                                        int64_t val_capacity,
-                                        int64_t* n_out_rows, void* hip_stream) {
-  if (!c || !cells || !n_out_rows) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  if (out && !out->row_series)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null output row_series");
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  bool identity = true;
-  return span_impl(c, cells, n_series, out, qual_capacity, val_capacity,
-                   n_out_rows, nullptr, nullptr, &identity, st);
-}
-
-otsdb_status otsdb_agg_run_raw_device(otsdb_ctx* c, const otsdb_query_spec* spec,
-                                      const otsdb_raw_rows* raw,
-                                      int32_t fix_duplicates,
-                                      const otsdb_batch* b, otsdb_result* out,
-                                      void* hip_stream) {
-  if (!c || !spec || !raw || !b || !out)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  DeviceCall dc(c, b, hip_stream);
-  otsdb_status rc = dc.rc;
-  if (!rc) rc = check_spec(spec);
-  if (!rc) rc = run_raw_impl(c, spec, raw, fix_duplicates != 0, b, out, dc.goff);
-  return rc;
-}
-
-// The host-pointer entries over storage rows: the rows, the groups and the
-// result staged in HBM; check: the entry's argument checks; run: its device
-// implementation over the staged copies.
-}  // extern "C" (a template has C++ linkage)
-template <class Check, class Run>
-static otsdb_status run_rows_host(otsdb_ctx* c, const otsdb_raw_rows* raw,
-                                  const otsdb_batch* b, otsdb_result* out,
-                                  Check check, Run run) {
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  otsdb_status rc = check();
-  if (rc) return rc;
-  std::vector<int64_t> goff;
-  if ((rc = read_goff(c, b, false, goff))) return rc;
-  const int64_t R = raw->n_rows, S = b->n_series, G = b->n_groups;
-  if (R < 0 || S < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
-  if (!raw->row_series || !raw->row_base_s || !raw->row_col_off ||
-      !raw->col_qual_off || !raw->col_val_off)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null raw row array");
-  const int64_t M = goff.back();
-  for (int64_t r = 0; r < R; ++r)
-    if (raw->row_series[r] < 0 || raw->row_series[r] >= S ||
-        (r && raw->row_series[r] < raw->row_series[r - 1]))
-      return fail(OTSDB_E_ILLEGAL_ARGUMENT,
-                  "row_series must be nondecreasing series indices");
-  for (int64_t m = 0; m < M; ++m)
-    if (b->group_members[m] < 0 || b->group_members[m] >= S)
-      return fail(OTSDB_E_ILLEGAL_ARGUMENT, "group member out of range");
-  const int64_t C = raw->row_col_off[R];
-  const int64_t QB = raw->col_qual_off[C], VB = raw->col_val_off[C];
-  const int64_t cap = out->capacity;
-  auto carve = [&](char* base) {
-    Carve cv{base};
-    void* p[14];
-    p[0] = cv.take<int64_t>(R + 1);
-    p[1] = cv.take<int64_t>(R + 1);
-    p[2] = cv.take<int64_t>(R + 1);
-    p[3] = cv.take<int64_t>(C + 1);
-    p[4] = cv.take<uint8_t>(QB + 16);
-    p[5] = cv.take<int64_t>(C + 1);
-    p[6] = cv.take<uint8_t>(VB + 16);
-    p[7] = raw->col_ts ? cv.take<int64_t>(C + 1) : nullptr;
-    p[8] = cv.take<int64_t>(G + 1);
-    p[9] = cv.take<int64_t>(M + 1);
-    p[10] = cv.take<int64_t>(G + 1);
-    p[11] = cv.take<int64_t>(cap + 1);
-    p[12] = cv.take<int64_t>(cap + 1);
-    p[13] = cv.take<uint8_t>(cap + 1);
-    return std::make_pair(cv.off + 256, std::vector<void*>(p, p + 14));
-  };
-  rc = ensure(&c->raw_stage, &c->raw_stage_cap, carve(nullptr).first);
-  if (rc) return rc;
-  auto pp = carve((char*)c->raw_stage).second;
-  hipStream_t st = c->stream;
-  auto h2d = [&](void* d, const void* h, size_t n) -> otsdb_status {
-    if (n && h) HIP_TRY(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, st));
-    return OTSDB_OK;
-  };
-  if ((rc = h2d(pp[0], raw->row_series, 8 * R)) ||
-      (rc = h2d(pp[1], raw->row_base_s, 8 * R)) ||
-      (rc = h2d(pp[2], raw->row_col_off, 8 * (R + 1))) ||
-      (rc = h2d(pp[3], raw->col_qual_off, 8 * (C + 1))) ||
-      (rc = h2d(pp[4], raw->qual, QB)) ||
-      (rc = h2d(pp[5], raw->col_val_off, 8 * (C + 1))) ||
-      (rc = h2d(pp[6], raw->val, VB)) ||
-      (rc = h2d(pp[7], raw->col_ts, 8 * C)) ||
-      (rc = h2d(pp[8], b->group_offsets, 8 * (G + 1))) ||
-      (rc = h2d(pp[9], b->group_members, 8 * M)))
-    return rc;
-  otsdb_raw_rows dr{R,
-                    (const int64_t*)pp[0],
-                    (const int64_t*)pp[1],
-                    (const int64_t*)pp[2],
-                    (const int64_t*)pp[3],
-                    (const uint8_t*)pp[4],
-                    (const int64_t*)pp[5],
-                    (const uint8_t*)pp[6],
-                    (const int64_t*)pp[7]};
-  otsdb_batch db = *b;
-  db.n_points = 0;
-  db.offsets = nullptr;
-  db.ts_ms = nullptr;
-  db.val = nullptr;
-  db.is_float = nullptr;
-  db.series_float = nullptr;
-  db.group_offsets = (const int64_t*)pp[8];
-  db.group_members = (const int64_t*)pp[9];
-  otsdb_result dres;
-  dres.capacity = cap;
-  dres.offsets = (int64_t*)pp[10];
-  dres.ts = (int64_t*)pp[11];
-  dres.val = (int64_t*)pp[12];
-  dres.is_int = (uint8_t*)pp[13];
-  c->result_short = false;
-  rc = run(&dr, &db, &dres, goff);
-  if (rc == OTSDB_E_CAPACITY && c->result_short)
-    return copy_offsets_back(c, out, dres.offsets, G, rc);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out->offsets, dres.offsets, 8 * (G + 1),
-                         hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const int64_t total = out->offsets[G];
-  if (total > 0) {
-    HIP_TRY(hipMemcpyAsync(out->ts, dres.ts, 8 * total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->val, dres.val, 8 * total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->is_int, dres.is_int, total, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  return OTSDB_OK;
-}
-extern "C" {
-
-otsdb_status otsdb_agg_run_raw(otsdb_ctx* c, const otsdb_query_spec* spec,
-                               const otsdb_raw_rows* raw, int32_t fix_duplicates,
-                               const otsdb_batch* b, otsdb_result* out) {
-  if (!c || !spec || !raw || !b || !out)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  return run_rows_host(
-      c, raw, b, out, [&] { return check_spec(spec); },
-      [&](const otsdb_raw_rows* dr, const otsdb_batch* db, otsdb_result* dres,
-          std::vector<int64_t>& goff) {
-        return run_raw_impl(c, spec, dr, fix_duplicates != 0, db, dres, goff);
-      });
-}
-
-otsdb_status otsdb_rollup_decode_rows_device(
-    otsdb_ctx* c, const otsdb_raw_rows* raw, const otsdb_rollup_table* table,
-    int32_t rollup_agg_id, int64_t n_series, int64_t seek_ms, int64_t* offsets,
-    int64_t* ts_ms, int64_t* val, uint8_t* is_float, int64_t* value_count,
-    int64_t capacity, void* hip_stream) {
-  // (the argument checks first: they need no context)
-  otsdb_status rc = check_rollup_table(raw, table, rollup_agg_id);
-  if (rc) return rc;
-  if (!c || !offsets) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  if (ts_ms && (!val || !is_float ||
-                (rollup_agg_id == OTSDB_AGG_AVG && !value_count)))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null output column");
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  return rollup_decode_impl(c, raw, table, rollup_agg_id, n_series, seek_ms,
-                            offsets, ts_ms, val, is_float, value_count,
-                            capacity, st);
-}
-
-// check_rollup's refusals with the counts still to come (the decode writes
-// them), then the table's
-static otsdb_status check_rollup_rows(const otsdb_query_spec* spec,
-                                      const otsdb_raw_rows* raw,
-                                      const otsdb_rollup_table* table,
-                                      int32_t agg) {
-  static const int64_t kPending = 0;
-  RollupKind kind;
-  const otsdb_status rc = check_rollup(spec, Rollup{agg, &kPending}, &kind);
-  return rc ? rc : check_rollup_table(raw, table, agg);
-}
-
-otsdb_status otsdb_agg_run_rollup_rows_device(
-    otsdb_ctx* c, const otsdb_query_spec* spec, const otsdb_raw_rows* raw,
-    const otsdb_rollup_table* table, int32_t rollup_agg_id,
-    const otsdb_batch* b, otsdb_result* out, void* hip_stream) {
-  if (!spec || !raw || !table || !b || !out)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  // (the argument checks first: they need no context)
-  const otsdb_status rc = check_rollup_rows(spec, raw, table, rollup_agg_id);
-  if (rc) return rc;
-  if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null context");
-  DeviceCall dc(c, b, hip_stream);
-  return dc.rc ? dc.rc
-               : run_rollup_rows_impl(c, spec, raw, table, rollup_agg_id, b,
-                                      out, dc.goff);
-}
-
-otsdb_status otsdb_agg_run_rollup_rows(otsdb_ctx* c,
-                                       const otsdb_query_spec* spec,
-                                       const otsdb_raw_rows* raw,
-                                       const otsdb_rollup_table* table,
-                                       int32_t rollup_agg_id,
-                                       const otsdb_batch* b,
-                                       otsdb_result* out) {
-  if (!spec || !raw || !table || !b || !out)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  // (the argument checks first: they need no context)
-  const otsdb_status rc = check_rollup_rows(spec, raw, table, rollup_agg_id);
-  if (rc) return rc;
-  if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null context");
-  return run_rows_host(
-      c, raw, b, out, [] { return OTSDB_OK; },
-      [&](const otsdb_raw_rows* dr, const otsdb_batch* db, otsdb_result* dres,
-          std::vector<int64_t>& goff) {
-        return run_rollup_rows_impl(c, spec, dr, table, rollup_agg_id, db,
-                                    dres, goff);
-      });
-}
-
 otsdb_status otsdb_agg_run_cells(otsdb_ctx* c, const otsdb_query_spec* spec,
                                  const otsdb_cells* cells, const otsdb_batch* b,
                                  otsdb_result* out) {
@@ -5973,9 +4459,9 @@ otsdb_status otsdb_agg_run_cells(otsdb_ctx* c, const otsdb_query_spec* spec,
     p[10] = cv.take<uint8_t>(cap + 1);
     return std::make_pair(cv.off + 256, std::vector<void*>(p, p + 11));
   };
-  rc = ensure(&c->raw_stage, &c->raw_stage_cap, carve(nullptr).first);
+  rc = c->raw_stage.ensure(carve(nullptr).first);
   if (rc) return rc;
-  auto pp = carve((char*)c->raw_stage).second;
+  auto pp = carve((char*)c->raw_stage.p).second;
   hipStream_t st = c->stream;
   auto h2d = [&](void* d, const void* h, size_t n) -> otsdb_status {
     if (n && h) HIP_TRY(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, st));
@@ -6126,228 +4612,6 @@ otsdb_status otsdb_gen_fill_device(otsdb_ctx* c, const otsdb_gen_spec* g,
     hipLaunchKernelGGL(k_gen_fill, dim3(blocks_for(n_series, 4)), dim3(256),
                        0, st, gp, series0, n_series, offsets, ts_ms, val);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
-  return OTSDB_OK;
-}
-
-// ---- histogram queries ---------------------------------------------------
-int32_t otsdb_hist_window(int32_t n_bins) {
-  if (n_bins < 1 || n_bins + 2 > kHistMaxRow) return 0;
-  return hist_window(n_bins + 2);
-}
-
-otsdb_status otsdb_hist_plan(otsdb_ctx*, const otsdb_query_spec* spec,
-                             const otsdb_batch* b, const otsdb_hist_columns* h,
-                             otsdb_sizes* out) {
-  if (!spec || !b || !h || !out) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  Params P;
-  otsdb_status rc = hist_check(spec, h, 0, &P);
-  if (rc) return rc;
-  if (b->n_groups < 0 || b->n_series < 0)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
-  const int R = h->n_bins + 2;
-  if ((rc = hist_dense_budget(b->n_groups, P.nb, R))) return rc;
-  out->n_buckets = P.nb;
-  out->max_out_points = b->n_groups * P.nb;
-  // the dense sums and percentiles, the series bounds, and one partial slot
-  // for each 64-member tile of a group of more than 64 members: counted from
-  // the host copy of the group offsets where the batch has one, else bounded
-  // for a batch that lists each series in one group (members / 64 slots plus
-  // one a group of 65 or more; a batch that lists series in several groups
-  // without a host copy takes more)
-  int64_t slots = 2 * (b->n_series / kHistTile) + 1;
-  if (b->group_offsets_host) {
-    slots = 0;
-    for (int64_t g = 0; g < b->n_groups; ++g) {
-      const int64_t k = b->group_offsets_host[g + 1] - b->group_offsets_host[g];
-      if (k > kHistTile) slots += (k + kHistTile - 1) / kHistTile;
-    }
-  }
-  out->workspace_bytes =
-      b->n_groups * P.nb * (8 * (int64_t)R + 8 * kHistMaxPct + 1) +
-      b->n_series * 16 + slots * P.nb * (8 * (int64_t)R + 1) +
-      ((int64_t)1 << 20);
-  return OTSDB_OK;
-}
-
-otsdb_status otsdb_hist_run_device(otsdb_ctx* c, const otsdb_query_spec* spec,
-                                   const otsdb_batch* b,
-                                   const otsdb_hist_columns* h,
-                                   const float* pcts, int32_t n_pct,
-                                   otsdb_hist_result* out, void* hip_stream) {
-  if (!spec || !b || !h || !out || (n_pct > 0 && !pcts))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  Params P;
-  otsdb_status rc = hist_check(spec, h, n_pct, &P);
-  if (!rc) rc = hist_out_check(out, n_pct);
-  if (!rc) rc = hist_dense_budget(b->n_groups, P.nb, h->n_bins + 2);
-  if (rc) return rc;
-  if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null context");
-  DeviceCall dc(c, b, hip_stream);
-  if (dc.rc) return dc.rc;
-  int64_t total = 0;
-  return hist_run_impl(c, spec, P, b, h, dc.goff, pcts, n_pct, out, &total);
-}
-
-otsdb_status otsdb_hist_partials_device(otsdb_ctx* c,
-                                        const otsdb_query_spec* spec,
-                                        const otsdb_batch* b,
-                                        const otsdb_hist_columns* h,
-                                        int64_t* dense, uint8_t* emit,
-                                        void* hip_stream) {
-  if (!spec || !b || !h || !dense || !emit)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  Params P;
-  otsdb_status rc = hist_check(spec, h, 0, &P);
-  if (!rc) rc = hist_dense_budget(b->n_groups, P.nb, h->n_bins + 2);
-  if (rc) return rc;
-  if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null context");
-  DeviceCall dc(c, b, hip_stream);
-  if (dc.rc) return dc.rc;
-  HistTiles T;
-  hist_tiles(dc.goff, &T);
-  const int R = h->n_bins + 2;
-  if ((rc = hist_partial_budget(T, P.nb, R))) return rc;
-  HistWork W;
-  const size_t need =
-      hist_carve(nullptr, &W, b->n_series, &T, b->n_groups, P.nb, R, 0, false);
-  if ((rc = ensure(&c->ws, &c->ws_cap, need))) return rc;
-  hist_carve((char*)c->ws, &W, b->n_series, &T, b->n_groups, P.nb, R, 0, false);
-  std::vector<int64_t> tbuf;
-  rc = hist_partials(c, spec, P, b, h, T, W, tbuf, dense, emit);
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return rc;
-}
-
-otsdb_status otsdb_hist_finalize_device(otsdb_ctx* c,
-                                        const otsdb_query_spec* spec,
-                                        const otsdb_hist_columns* h,
-                                        int64_t n_groups, int64_t n_buckets,
-                                        const int64_t* dense,
-                                        const uint8_t* emit, const float* pcts,
-                                        int32_t n_pct, otsdb_hist_result* out,
-                                        void* hip_stream) {
-  if (!spec || !h || !dense || !emit || !out || (n_pct > 0 && !pcts))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  Params P;
-  otsdb_status rc = hist_check(spec, h, n_pct, &P);
-  if (!rc) rc = hist_out_check(out, n_pct);
-  if (rc) return rc;
-  if (n_groups < 0 || n_buckets != P.nb)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT,
-                "n_buckets %lld is not the plan's %lld", (long long)n_buckets,
-                (long long)P.nb);
-  if ((rc = hist_dense_budget(n_groups, P.nb, h->n_bins + 2))) return rc;
-  if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null context");
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  StreamBinding bind(c, hip_stream);
-  HistWork W;
-  const int R = h->n_bins + 2;
-  const size_t need =
-      hist_carve(nullptr, &W, 0, nullptr, n_groups, P.nb, R, n_pct, false);
-  if ((rc = ensure(&c->ws, &c->ws_cap, need))) return rc;
-  hist_carve((char*)c->ws, &W, 0, nullptr, n_groups, P.nb, R, n_pct, false);
-  int64_t total = 0;
-  return hist_finalize(c, P, n_groups, h, W, dense, emit, pcts, n_pct, out,
-                       &total);
-}
-
-otsdb_status otsdb_hist_run(otsdb_ctx* c, const otsdb_query_spec* spec,
-                            const otsdb_batch* b, const otsdb_hist_columns* h,
-                            const float* pcts, int32_t n_pct,
-                            otsdb_hist_result* out) {
-  if (!spec || !b || !h || !out || (n_pct > 0 && !pcts))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
-  Params P;
-  otsdb_status rc = hist_check(spec, h, n_pct, &P);
-  if (!rc) rc = hist_out_check(out, n_pct);
-  if (!rc) rc = hist_dense_budget(b->n_groups, P.nb, h->n_bins + 2);
-  if (rc) return rc;
-  if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null context");
-  CtxLock lk(c);
-  HIP_TRY(hipSetDevice(c->device));
-  std::vector<int64_t> goff;
-  if ((rc = read_goff(c, b, false, goff))) return rc;
-  const int64_t S = b->n_series, N = b->n_points, G = b->n_groups;
-  const int64_t M = goff.back(), cap = out->capacity;
-  const int R = h->n_bins + 2;
-  if (S < 0 || N < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
-  if (S > 0 && (!b->offsets || b->offsets[S] != N))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "offsets[S] != n_points");
-  if (N > 0 && (!b->ts_ms || !h->counts))
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null batch column");
-  if (M > 0 && !b->group_members)
-    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "no group members");
-  for (int64_t s = 0; s < S; ++s)
-    if (b->offsets[s] < 0 || b->offsets[s + 1] < b->offsets[s])
-      return fail(OTSDB_E_ILLEGAL_ARGUMENT, "offsets not monotonic");
-  for (int64_t m = 0; m < M; ++m)
-    if (b->group_members[m] < 0 || b->group_members[m] >= S)
-      return fail(OTSDB_E_ILLEGAL_ARGUMENT, "group member out of range");
-  // staging layout in HBM: the batch, then the result
-  struct Stage {
-    int64_t *off, *ts, *cnt, *goff, *mem, *r_off, *r_ts, *r_cnt;
-    double* r_pct;
-  } D;
-  auto carve = [&](char* base) {
-    Carve cv{base};
-    D.off = cv.take<int64_t>(S + 1);
-    D.ts = cv.take<int64_t>(N + 1);
-    D.cnt = cv.take<int64_t>((size_t)N * R + 2);
-    D.goff = cv.take<int64_t>(G + 1);
-    D.mem = cv.take<int64_t>(M + 1);
-    D.r_off = cv.take<int64_t>(G + 1);
-    D.r_ts = cv.take<int64_t>(cap + 1);
-    D.r_pct = cv.take<double>((size_t)n_pct * cap + 1);
-    D.r_cnt = cv.take<int64_t>(out->counts ? (size_t)cap * R + 1 : 1);
-    return cv.off + 256;
-  };
-  if ((rc = ensure(&c->stage, &c->stage_cap, carve(nullptr)))) return rc;
-  carve((char*)c->stage);
-  hipStream_t st = c->stream;
-  auto h2d = [&](void* d, const void* hsrc, size_t n) -> otsdb_status {
-    if (n && hsrc) HIP_TRY(hipMemcpyAsync(d, hsrc, n, hipMemcpyHostToDevice, st));
-    return OTSDB_OK;
-  };
-  if ((rc = h2d(D.off, b->offsets, 8 * (size_t)(S + 1)))) return rc;
-  if ((rc = h2d(D.ts, b->ts_ms, 8 * (size_t)N))) return rc;
-  if ((rc = h2d(D.cnt, h->counts, 8 * (size_t)N * R))) return rc;
-  if ((rc = h2d(D.goff, b->group_offsets, 8 * (size_t)(G + 1)))) return rc;
-  if ((rc = h2d(D.mem, b->group_members, 8 * (size_t)M))) return rc;
-  otsdb_batch db = *b;
-  db.offsets = D.off;
-  db.ts_ms = D.ts;
-  db.val = nullptr;
-  db.is_float = db.series_float = nullptr;
-  db.group_offsets = D.goff;
-  db.group_members = D.mem;
-  otsdb_hist_columns dh = *h;
-  dh.counts = D.cnt;
-  otsdb_hist_result dr{cap, D.r_off, D.r_ts, n_pct > 0 ? D.r_pct : nullptr,
-                       out->counts ? D.r_cnt : nullptr};
-  c->result_short = false;
-  int64_t total = 0;
-  rc = hist_run_impl(c, spec, P, &db, &dh, goff, pcts, n_pct, &dr, &total);
-  if (rc == OTSDB_E_CAPACITY && c->result_short) {
-    // the offsets the whole result needs, then the status
-    hipMemcpyAsync(out->offsets, D.r_off, 8 * (G + 1), hipMemcpyDeviceToHost, st);
-    hipStreamSynchronize(st);
-    return rc;
-  }
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out->offsets, D.r_off, 8 * (G + 1),
-                         hipMemcpyDeviceToHost, st));
-  if (total > 0) {
-    HIP_TRY(hipMemcpyAsync(out->ts, D.r_ts, 8 * total, hipMemcpyDeviceToHost, st));
-    for (int q = 0; q < n_pct; ++q)
-      HIP_TRY(hipMemcpyAsync(out->pct_val + (size_t)q * cap,
-                             D.r_pct + (size_t)q * cap, 8 * total,
-                             hipMemcpyDeviceToHost, st));
-    if (out->counts)
-      HIP_TRY(hipMemcpyAsync(out->counts, D.r_cnt, 8 * (size_t)total * R,
-                             hipMemcpyDeviceToHost, st));
-  }
   HIP_TRY(hipStreamSynchronize(st));
   return OTSDB_OK;
 }

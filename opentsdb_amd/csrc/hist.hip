@@ -1,7 +1,7 @@
 // hist.hip — histogram queries (otsdb_hist_*): the members'
 // histogram points are downsampled and summed across each group on the GPU,
 // the percentiles read off the sums.  gfx950, wave64, integer arithmetic only
-// up to the percentile's `area`.  (Included by engine.hip after kernels.hip
+// up to the percentile's `area`.  (Included by engine_hist.hip after kernels.hip
 // and compact.hip: Params, bucket_of, bucket_ts, lower_bound_interp,
 // compact_count, LANE.)
 //

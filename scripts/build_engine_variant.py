@@ -1,6 +1,7 @@
-"""An engine-only tuning variant: engine.hip compiled with extra -D flags and
-linked with the production build's downsampling objects (for knobs that only
-engine.hip's kernels read, e.g. compact.hip's).  Usage:
+"""An engine-only tuning variant: the engine units (build.ENGINE_UNITS)
+compiled with extra -D flags and linked with the production build's
+downsampling objects (for knobs that only the engine units' kernels read,
+e.g. compact.hip's).  Usage:
 python scripts/build_engine_variant.py name=DEF[,DEF...]"""
 import os
 import subprocess
@@ -15,12 +16,14 @@ for arg in sys.argv[1:]:
     name, _, defs = arg.partition("=")
     d = os.path.join(build.OUT_DIR, "var_" + name)
     os.makedirs(d, exist_ok=True)
-    eng = os.path.join(d, "engine.o")
-    subprocess.check_call([build.HIPCC] + build.FLAGS +
-                          ["-D" + x for x in defs.split(",") if x] +
-                          ["-c", "-o", eng,
-                           os.path.join(build.CSRC, "engine.hip")])
-    objs = [eng] + [u[2] for u in build._units(build.OUT_DIR, ())[1:]]
+    objs = []
+    for src, _, obj, kind in build._units(build.OUT_DIR, ()):
+        if kind in build.ENGINE_UNITS:
+            obj = os.path.join(d, os.path.basename(obj))
+            subprocess.check_call([build.HIPCC] + build.FLAGS +
+                                  ["-D" + x for x in defs.split(",") if x] +
+                                  ["-c", "-o", obj, src])
+        objs.append(obj)
     out = os.path.join(d, "libotsdb_agg.so")
     subprocess.check_call([build.HIPCC, "--offload-arch=" + build.ARCH,
                            "-shared", "-fPIC", "-o", out] + objs)

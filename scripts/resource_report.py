@@ -1,14 +1,19 @@
-"""The compiler's gfx950 resource report of every kernel of engine.hip
+"""The compiler's gfx950 resource report of every kernel of the engine units
 (hipcc -Rpass-analysis=kernel-resource-usage, build.py's flags), for this tree
 and, with --before, for another checkout of the project (the parent commit):
 which kernels exist on both sides, whether their figures are identical, and
-the figures of the kernels whose names match --new.  --ds-monoids compares
-the ds_tu.hip units of those downsampling monoids as well, both parts.
+the figures of the kernels whose names match --new.  The engine units of a
+tree are those its build.py lists (ENGINE_UNITS; a checkout without the list
+has engine.hip alone), reported as one set: a kernel that moved between
+units compares equal, one that two units define is listed.  --ds-monoids
+compares the ds_tu.hip units of those downsampling monoids as well, both
+parts.
 
     python -m scripts.resource_report --before PATH/TO/PARENT/CHECKOUT \
         --new k_rr_ --out profiles/rollup_rows_resources.json
 """
 import argparse
+import importlib.util
 import json
 import os
 import re
@@ -48,6 +53,30 @@ def report(root, unit="engine.hip", defines=()):
     return {d or n: out[n] for n, d in zip(names, dem)}
 
 
+def engine_units(root):
+    """The engine units' sources of the checkout at root."""
+    spec = importlib.util.spec_from_file_location(
+        "_otsdb_build_of_" + str(abs(hash(root))),
+        os.path.join(root, "opentsdb_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    if not hasattr(mod, "ENGINE_UNITS"):
+        return ["engine.hip"]
+    return [mod.UNIT_FILES[k][0] for k in mod.ENGINE_UNITS]
+
+
+def report_engine(root):
+    """(the union of report() over root's engine units, the kernels more than
+    one of them defines)."""
+    out, twice = {}, []
+    for unit in engine_units(root):
+        for k, v in report(root, unit).items():
+            if k in out:
+                twice.append(k)
+            out[k] = v
+    return out, sorted(twice)
+
+
 def compare(before, after):
     return {"kernels_before": len(before), "kernels_after": len(after),
             "kernels_only_before": sorted(set(before) - set(after)),
@@ -65,7 +94,9 @@ def main():
                     help="comma-separated OTSDB_DS_MONOID values")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    after = report(ROOT)
+    ds = [("ds_tu.hip", ("OTSDB_DS_MONOID=" + m, "OTSDB_DS_PART=%d" % part))
+          for m in filter(None, a.ds_monoids.split(",")) for part in (1, 0)]
+    after, twice = report_engine(ROOT)
     doc = {"arch": "gfx950",
            "source": "hipcc " + " ".join(__import__(
                "opentsdb_amd.build", fromlist=["FLAGS"]).FLAGS[1:5]) +
@@ -73,15 +104,14 @@ def main():
            "entry below; before = the parent commit",
            "new": {k: v for k, v in after.items() if a.new in k}}
     if a.before:
-        before = report(a.before)
+        before, _ = report_engine(a.before)
         old = {k: v for k, v in after.items() if a.new not in k}
-        doc["engine.hip"] = compare(before, old)
-        for m in filter(None, a.ds_monoids.split(",")):
-            for part in (0, 1):
-                d = ("OTSDB_DS_MONOID=" + m, "OTSDB_DS_PART=%d" % part)
-                doc["ds_tu.hip " + " ".join("-D" + x for x in d)] = compare(
-                    report(a.before, "ds_tu.hip", d),
-                    report(ROOT, "ds_tu.hip", d))
+        doc["engine units"] = dict(
+            compare(before, old), units_before=engine_units(a.before),
+            units_after=engine_units(ROOT), kernels_in_several_units=twice)
+        for unit, d in sorted(ds):
+            doc[unit + " " + " ".join("-D" + x for x in d)] = compare(
+                report(a.before, unit, d), report(ROOT, unit, d))
     print(json.dumps(doc, indent=1))
     if a.out:
         with open(a.out, "w") as f:
