@@ -936,8 +936,9 @@ otsdb_status otsdb_agg_run_rollup_rows(
  * underflow and overflow; one point is one contiguous record (8-byte aligned;
  * 16-byte loads when K is even and the matrix 16-byte aligned).  A HOST
  * pointer for otsdb_hist_run, a DEVICE pointer for the _device entries.
- * Decoding the stored blobs stays with the caller (codecs are plugins,
- * HistogramCodecManager; the Java side holds decoded objects).  The schema is
+ * Decoding the stored blobs stays with the caller here (codecs are plugins,
+ * HistogramCodecManager; the Java side holds decoded objects);
+ * otsdb_hist_run_rows below decodes SimpleHistogramDecoder's.  The schema is
  * the union of the keys of every histogram of the query; a histogram that
  * lacks a key passes 0 there.  A zero-count key can never be the one a
  * percentile picks — its area equals its predecessor's, which did not
@@ -1025,6 +1026,104 @@ otsdb_status otsdb_hist_finalize_device(otsdb_ctx* ctx,
  * results; tests take the window edges from it.                            */
 int32_t otsdb_hist_window(int32_t n_bins);
 
+/* ---- histogram queries from storage rows --------------------------------- */
+/* The histogram query from what the scanner delivers: `raw` holds the rows,
+ * one entry per (series, base hour), row_series nondecreasing (col_ts is not
+ * read); the stored blobs are decoded on the device for the one codec the
+ * reference ships, SimpleHistogramDecoder, whose id in
+ * tsd.core.histograms.config is simple_codec_id (0..255).
+ *
+ * A histogram cell is a column whose qualifier has odd length and starts
+ * with 0x06 (HistogramDataPoint.PREFIX; CompactionQueue.java:441-452,
+ * SaltScanner.java:788-795); every other column — data cells, compacted
+ * columns, appends, annotations, an even-length 06 xx — is ignored.
+ * Timestamp (Internal.getTimeStampFromNonDP, Internal.java:1059-1074): a
+ * 3-byte qualifier gives (base_s + (signed q[1] << 8 | q[2])) * 1000, a
+ * 5-byte one base_s * 1000 + int32(q[1..4] big-endian).  Value
+ * (Internal.decodeHistogramDataPoint :1095-1104, SimpleHistogram.fromHistogram
+ * SimpleHistogram.java:97-122): the id byte, a big-endian signed short
+ * bucketCount, bucketCount times {float lower, float upper (big-endian IEEE
+ * bits), var-long count}, then var-long underflow and overflow; trailing
+ * bytes are ignored, bucketCount <= 0 reads no bucket, a key repeated in one
+ * blob keeps the later count, keys are equal when Float.compare is 0 on both
+ * bounds (every NaN one key).  The var-long is Kryo 3.0.0's
+ * Output.writeLong(v, true): 7 value bits a byte from the least significant
+ * group, bit 7 "another byte follows", a ninth byte taken whole (1..9 bytes,
+ * a negative long always 9).  The byte format is pinned by the hand-derived
+ * vectors of tests/golden/kat_hist_rows.json, not by a run of the reference.
+ * What throws in the reference's decode is logged and SKIPPED there
+ * (catch Throwable) and here — an empty value or one under 6 bytes, a read
+ * past the value's end, a qualifier of odd length other than 3 or 5: the
+ * point does not exist, and a row left without one is no row.
+ * Span assembly (HistogramSpan.addRow :280-328, HistogramRowSeq.addRow
+ * :66-105): a row's points are its surviving cells in column order;
+ * consecutive rows of one series and base time are one row sequence, merged
+ * by timestamp, the earlier row keeping an equal one.
+ *
+ * Deviations, all OTSDB_E_UNSUPPORTED: a cell whose id byte is not
+ * simple_codec_id (another codec may decode it in the reference; checked
+ * after the qualifier's length, before the value's); bucketCount > 254,
+ * checked before the walk (the reference would read on); timestamps that do
+ * not strictly increase along a row's surviving cells (the reference keeps
+ * column order); base times that decrease inside a series in arrival order
+ * (the reference's out-of-order replay is not restated); more than 64
+ * consecutive rows of one key; an assembled series whose timestamps do not
+ * strictly increase from one row sequence to the next (offsets that leave
+ * the row's hour).  A decodable cell's key outside the supplied schema:
+ * OTSDB_E_ILLEGAL_ARGUMENT.  The first failing row in row order, then the
+ * first failing column in it, decides the status (a failure of the row as a
+ * whole counts before its columns; the cross-row timestamp check is made
+ * when nothing else failed).  NULL raw or arrays, simple_codec_id outside
+ * 0..255, and on the decode and query entries a NULL hist / schema or
+ * n_bins < 1: OTSDB_E_ILLEGAL_ARGUMENT, before any device work.
+ *
+ * otsdb_ctx_counters, of the last of these calls: [15] histogram cells
+ * decoded into points, [16] cells skipped as undecodable (what the reference
+ * logs), [17] points dropped by a same-key merge.                           */
+
+/* The query's bucket schema: the union of the keys of every cell that
+ * decodes, sorted in TreeMap order into HOST arrays of OTSDB_HIST_MAX_ROW - 2
+ * floats; *n_bins may come back 0.  More than 254 distinct keys:
+ * OTSDB_E_UNSUPPORTED.  raw: DEVICE pointers.  Synchronous.                 */
+otsdb_status otsdb_hist_rows_schema_device(otsdb_ctx* ctx, const otsdb_raw_rows* raw,
+                                           int32_t simple_codec_id,
+                                           float* lower, float* upper,
+                                           int32_t* n_bins, void* hip_stream);
+/* The decode alone, otsdb_rollup_decode_rows_device's contract: hist gives
+ * the schema (its counts is not read); offsets [n_series + 1], ts_ms [N] and
+ * counts [N][K + 2] are DEVICE pointers; ts_ms == NULL only counts (offsets
+ * filled, offsets[n_series] the points).  Keys a blob lacks are 0, columns K
+ * and K + 1 the underflow and overflow.  capacity below the points:
+ * OTSDB_E_CAPACITY.                                                         */
+otsdb_status otsdb_hist_decode_rows_device(otsdb_ctx* ctx, const otsdb_raw_rows* raw,
+                                           int32_t simple_codec_id,
+                                           int64_t n_series,
+                                           const otsdb_hist_columns* hist,
+                                           int64_t* offsets, int64_t* ts_ms,
+                                           int64_t* counts, int64_t capacity,
+                                           void* hip_stream);
+/* The query from the rows: the decode above into a context-owned buffer,
+ * then exactly what otsdb_hist_run_device runs on those columns (the same
+ * refusals, limits and result layout; otsdb_ctx_counters [13], [14] alike).
+ * `batch` supplies n_series and the groups only; `hist` the schema, required
+ * (otsdb_hist_rows_schema_device finds it).  _device: DEVICE pointers;
+ * otsdb_hist_run_rows: HOST pointers, synchronous.                          */
+otsdb_status otsdb_hist_run_rows_device(otsdb_ctx* ctx, const otsdb_query_spec* spec,
+                                        const otsdb_raw_rows* raw,
+                                        int32_t simple_codec_id,
+                                        const otsdb_batch* batch,
+                                        const otsdb_hist_columns* hist,
+                                        const float* percentiles, int32_t n_pct,
+                                        otsdb_hist_result* out,
+                                        void* hip_stream);
+otsdb_status otsdb_hist_run_rows(otsdb_ctx* ctx, const otsdb_query_spec* spec,
+                                 const otsdb_raw_rows* raw,
+                                 int32_t simple_codec_id,
+                                 const otsdb_batch* batch,
+                                 const otsdb_hist_columns* hist,
+                                 const float* percentiles, int32_t n_pct,
+                                 otsdb_hist_result* out);
+
 /* ---- stage timing (bench roofline) ------------------------------------- */
 /* When enabled, every query records HIP events around its pipeline stages
  * on the query's stream.  otsdb_prof_read returns, per stage, the summed
@@ -1033,7 +1132,8 @@ int32_t otsdb_hist_window(int32_t n_bins);
  * [4] k_compact+k_scan; [5] query-time compaction, [6] span assembly, [7] the
  * decode into the context's columnar buffer (compacted cells, rollup rows);
  * histogram queries: [8] k_hist_prep + k_hist_fold, [9] k_hist_combine,
- * [10] k_hist_percentiles, [11] their compaction (n up to 12).
+ * [10] k_hist_percentiles, [11] their compaction; [12] the decode of
+ * histogram storage rows (otsdb_hist_run_rows*) (n up to 13).
  * Synchronises the stream.                                                  */
 otsdb_status otsdb_prof_enable(otsdb_ctx* ctx, int enable);
 otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
@@ -1058,7 +1158,10 @@ otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
  * OTSDB_SPEC_CELLS_MULTI_FOLD: one per cells fold launched, 2 after a uniform
  * miss).  Of the last otsdb_hist_* call: out[13] k_hist_fold launches (one
  * aggregation, whatever the number of percentiles), out[14] percentile
- * passes over the dense sums (1, or 0 when n_pct == 0).                     */
+ * passes over the dense sums (1, or 0 when n_pct == 0).  Of the last
+ * otsdb_hist_*rows* call: out[15] histogram cells decoded into points,
+ * out[16] cells skipped as undecodable, out[17] points dropped by a same-key
+ * merge.                                                                    */
 otsdb_status otsdb_ctx_counters(otsdb_ctx* ctx, int64_t* out, int n);
 /* Test hook: the one-pass compaction's epoch (1 .. 2^24 - 1, forward only)
  * the context's next call increments, so tests can drive it to its wrap.  */

@@ -200,6 +200,8 @@ EXPORTS = [
     "otsdb_hist_plan", "otsdb_hist_run", "otsdb_hist_run_device",
     "otsdb_hist_partials_device", "otsdb_hist_finalize_device",
     "otsdb_hist_window",
+    "otsdb_hist_rows_schema_device", "otsdb_hist_decode_rows_device",
+    "otsdb_hist_run_rows_device", "otsdb_hist_run_rows",
 ]
 
 MULTI_MAX = 32  # OTSDB_MULTI_MAX
@@ -372,6 +374,24 @@ def load(path=None):
         lib.otsdb_hist_finalize_device.restype = C.c_int
         lib.otsdb_hist_window.argtypes = [i32]
         lib.otsdb_hist_window.restype = i32
+    # histogram queries from storage rows: (ctx, raw, codec_id, lower, upper,
+    # n_bins, stream), (ctx, raw, codec_id, n_series, hist, offsets, ts_ms,
+    # counts, capacity, stream), (ctx, spec, raw, codec_id, batch, hist,
+    # percentiles, n_pct, result [, stream])
+    if hasattr(lib, "otsdb_hist_run_rows"):
+        PH, PHR = C.POINTER(HistColumns), C.POINTER(HistResult)
+        lib.otsdb_hist_rows_schema_device.argtypes = [
+            vp, PW, i32, vp, vp, C.POINTER(i32), vp]
+        lib.otsdb_hist_rows_schema_device.restype = C.c_int
+        lib.otsdb_hist_decode_rows_device.argtypes = [
+            vp, PW, i32, i64, PH, vp, vp, vp, i64, vp]
+        lib.otsdb_hist_decode_rows_device.restype = C.c_int
+        lib.otsdb_hist_run_rows_device.argtypes = [vp, PS, PW, i32, PB, PH, vp,
+                                                   i32, PHR, vp]
+        lib.otsdb_hist_run_rows_device.restype = C.c_int
+        lib.otsdb_hist_run_rows.argtypes = [vp, PS, PW, i32, PB, PH, vp, i32,
+                                            PHR]
+        lib.otsdb_hist_run_rows.restype = C.c_int
     # bound only on the ABI it was added to: a stale library of another
     # version must not hand out a symbol of other arguments
     if lib.otsdb_abi_version() == 6 and hasattr(lib, "otsdb_sel_retarget"):

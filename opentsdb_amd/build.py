@@ -11,7 +11,8 @@ rebuilt when one of those, or include/otsdb_agg.h, is newer than its object):
   context, planning, the pipeline, multi / panel / cells / selection queries,
   the non-template kernels of kernels.hip and the aggregator-templated ones),
   csrc/engine_rows.hip (storage rows and rollup rows: rows.hip,
-  rollup_rows.hip) and csrc/engine_hist.hip (histogram queries: hist.hip);
+  rollup_rows.hip) and csrc/engine_hist.hip (histogram queries: hist.hip,
+  hist_rows.hip);
   csrc/engine_int.h is what they share;
 - two units per downsampling monoid (csrc/ds_tu.hip with -DOTSDB_DS_MONOID=n:
   the downsample / ordered-fold kernels of that monoid, and with
@@ -57,7 +58,7 @@ UNIT_FILES = {
     "engine_rows": ("engine_rows.hip", "engine_int.h", "decode.hip",
                     "rows.hip", "rollup_rows.hip") + _SHARED,
     "engine_hist": ("engine_hist.hip", "engine_int.h", "compact.hip",
-                    "hist.hip", "histplan.h") + _SHARED,
+                    "hist.hip", "hist_rows.hip", "histplan.h") + _SHARED,
     "rollup": ("rollup.hip",) + _SHARED,
     "ds": _DS,                          # ds_tu.hip, -DOTSDB_DS_PART=0
     "cells": _DS + ("cellfold.hip",),   # ds_tu.hip, -DOTSDB_DS_PART=1

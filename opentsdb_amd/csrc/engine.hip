@@ -4540,12 +4540,12 @@ otsdb_status otsdb_prof_read(otsdb_ctx* c, double* ms, int64_t* launches,
   }
   c->ev_pending.clear();
   c->ev_used = 0;
-  for (int i = 0; i < n && i < 12; ++i) {
+  for (int i = 0; i < n && i < 13; ++i) {
     if (ms) ms[i] = c->prof_ms[i];
     if (launches) launches[i] = c->prof_n[i];
   }
   if (reset)
-    for (int i = 0; i < 12; ++i) {
+    for (int i = 0; i < 13; ++i) {
       c->prof_ms[i] = 0;
       c->prof_n[i] = 0;
     }
@@ -4555,14 +4555,15 @@ otsdb_status otsdb_prof_read(otsdb_ctx* c, double* ms, int64_t* launches,
 otsdb_status otsdb_ctx_counters(otsdb_ctx* c, int64_t* out, int n) {
   if (!c || (n > 0 && !out)) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
   CtxLock lk(c, /*keep_session=*/true);
-  const int64_t v[15] = {c->n_cells_uniform, c->n_cells_general,
+  const int64_t v[18] = {c->n_cells_uniform, c->n_cells_general,
                          c->n_cells_uni_miss, c->sel.key_reads, c->sel.passes,
                          c->n_multi_ds,       c->n_multi_group, c->n_multi_kt,
                          c->n_multi_tf,       c->sel.sessions,
                          c->n_panel_passes,   c->n_panel_mats,
                          c->n_multi_fold,     c->n_hist_fold,
-                         c->n_hist_pct};
-  for (int i = 0; i < n && i < 15; ++i) out[i] = v[i];
+                         c->n_hist_pct,       c->n_hr_decoded,
+                         c->n_hr_skipped,     c->n_hr_dropped};
+  for (int i = 0; i < n && i < 18; ++i) out[i] = v[i];
   return OTSDB_OK;
 }
 

@@ -136,8 +136,8 @@ struct otsdb_ctx {
   std::vector<hipEvent_t> ev_pool;
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev_pending;
   size_t ev_used = 0;
-  double prof_ms[12] = {0};
-  int64_t prof_n[12] = {0};
+  double prof_ms[13] = {0};
+  int64_t prof_n[13] = {0};
   DevBuf cells_ws;   // cells query: series row / point offsets
   DevBuf cells_col;  // cells query fallback: decoded columns
   DevBuf cal;        // calendar bucket edges of the current query
@@ -184,6 +184,10 @@ struct otsdb_ctx {
   // otsdb_ctx_counters [13..14], of the last otsdb_hist_* call: k_hist_fold
   // launches, percentile passes over the dense sums
   int64_t n_hist_fold = 0, n_hist_pct = 0;
+  // otsdb_ctx_counters [15..17], of the last otsdb_hist_*rows* call: cells
+  // decoded into points, cells skipped as undecodable, points dropped by a
+  // same-key merge
+  int64_t n_hr_decoded = 0, n_hr_skipped = 0, n_hr_dropped = 0;
   // cross-rank selection session (otsdb_sel_*): lives in `ws` between calls
   struct {
     bool active = false;

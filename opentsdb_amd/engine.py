@@ -410,6 +410,74 @@ class Engine:
                            None if cnt is None else cnt[offs[g]:offs[g + 1]])
                 for g in range(G)]
 
+    def hist_rows_counters(self):
+        """Of the last histogram call from storage rows (otsdb_ctx_counters
+        [15..17]): cells decoded into points, cells skipped as undecodable
+        (what the reference logs), points dropped by a same-key merge."""
+        out = self._counters(18)
+        return dict(decoded=int(out[15]), skipped=int(out[16]),
+                    merged_away=int(out[17]))
+
+    def hist_rows_schema(self, rows, codec_id, stream=None):
+        """otsdb_hist_rows_schema_device: the bucket schema of the rows (a
+        storage.HostRawRows, copied to the device, or a DeviceRawRows) — the
+        sorted union of the keys of every cell that decodes with the
+        SimpleHistogramDecoder of id `codec_id`.  Returns (lower, upper)
+        float32 arrays of K entries (K may be 0)."""
+        draw = rows.to_device() if hasattr(rows, "to_device") else rows
+        lower = np.zeros(abi.HIST_MAX_ROW - 2, np.float32)
+        upper = np.zeros(abi.HIST_MAX_ROW - 2, np.float32)
+        n = C.c_int32(0)
+        raw = draw.as_abi()
+        self._check(self.lib.otsdb_hist_rows_schema_device(
+            self.ctx, C.byref(raw), int(codec_id), lower.ctypes.data,
+            upper.ctypes.data, C.byref(n), _stream(stream)))
+        return lower[:n.value].copy(), upper[:n.value].copy()
+
+    def run_hist_rows(self, spec, rows, codec_id, batch, percentiles,
+                      schema=None, want_counts=False):
+        """run_hist() from the scanner's storage rows (host arrays): `rows`
+        is a storage.HostRawRows, `codec_id` the id
+        tsd.core.histograms.config gives SimpleHistogramDecoder, `batch`
+        supplies n_series and the groups (its point arrays are not read) and
+        `schema` = (lower, upper) the bucket schema, found with
+        hist_rows_schema() when None.  The blobs are decoded on the device.
+        Results as run_hist()'s; rows without a decodable bucket give no
+        points."""
+        from .histogram import percentile_spec
+        p = percentile_spec(percentiles)
+        if schema is None:
+            schema = self.hist_rows_schema(rows, codec_id)
+        lower = np.ascontiguousarray(schema[0], dtype=np.float32)
+        upper = np.ascontiguousarray(schema[1], dtype=np.float32)
+        G, K, n = batch.n_groups, len(lower), len(p)
+        if K == 0:
+            return [HistPoints(np.zeros(0, np.int64), np.zeros((n, 0)),
+                               np.zeros((0, 2), np.int64) if want_counts
+                               else None) for _ in range(G)]
+        h = abi.HistColumns(K, lower.ctypes.data, upper.ctypes.data, None)
+        b = _groups_abi(batch)
+        sz = abi.Sizes()
+        self._check(self.lib.otsdb_hist_plan(self.ctx, C.byref(spec),
+                                             C.byref(b), C.byref(h),
+                                             C.byref(sz)))
+        cap = max(1, int(sz.max_out_points))
+        offs = np.zeros(G + 1, np.int64)
+        ts = np.zeros(cap, np.int64)
+        pct = np.zeros((max(n, 1), cap), np.float64)
+        cnt = np.zeros((cap, K + 2), np.int64) if want_counts else None
+        r = abi.HistResult(cap, offs.ctypes.data, ts.ctypes.data,
+                           pct.ctypes.data if n else None,
+                           None if cnt is None else cnt.ctypes.data)
+        raw = rows.as_abi()
+        self._check(self.lib.otsdb_hist_run_rows(
+            self.ctx, C.byref(spec), C.byref(raw), int(codec_id), C.byref(b),
+            C.byref(h), p.ctypes.data if n else None, n, C.byref(r)))
+        return [HistPoints(ts[offs[g]:offs[g + 1]],
+                           pct[:n, offs[g]:offs[g + 1]],
+                           None if cnt is None else cnt[offs[g]:offs[g + 1]])
+                for g in range(G)]
+
     def plan_multi(self, spec, aggs, batch, interps=None):
         n, ids, it = multi_args(aggs, interps)
         sz = abi.Sizes()
@@ -826,3 +894,55 @@ def hist_finalize_device(engine, spec, dhist, n_groups, n_buckets, dense,
         engine.ctx, C.byref(spec), C.byref(h), int(n_groups), int(n_buckets),
         dense.data_ptr(), emit.data_ptr(), pp, n, C.byref(r),
         _stream(stream)))
+
+
+def run_hist_rows_device(engine, spec, draw, codec_id, dbatch, dhist,
+                         percentiles, dresult, stream=None):
+    """Device-resident Engine.run_hist_rows: `draw` is a
+    storage.DeviceRawRows, `dbatch` supplies n_series and the groups,
+    `dhist` (a DeviceHist, counts None) the schema; the result lands in
+    `dresult`, a DeviceHistResult."""
+    p, pp, n = _pct_arg(percentiles)
+    b = abi.Batch()
+    b.n_series = dbatch.n_series
+    b.n_points = 0
+    b.n_groups = dbatch.n_groups
+    b.group_offsets = dbatch.group_offsets.data_ptr()
+    b.group_members = dbatch.group_members.data_ptr()
+    raw, h, r = draw.as_abi(), dhist.as_abi(), dresult.as_abi()
+    engine._check(engine.lib.otsdb_hist_run_rows_device(
+        engine.ctx, C.byref(spec), C.byref(raw), int(codec_id), C.byref(b),
+        C.byref(h), pp, n, C.byref(r), _stream(stream)))
+
+
+def hist_decode_rows_device(engine, draw, codec_id, n_series, schema,
+                            stream=None, counts_offset=0):
+    """otsdb_hist_decode_rows_device: the histogram cells of the rows (a
+    storage.DeviceRawRows) decoded into torch tensors (offsets
+    [n_series + 1], ts_ms [N], counts [N][K + 2]) on the rows' device over
+    `schema` = (lower, upper).  counts_offset: int64 words the count matrix
+    is displaced by inside its allocation (tests: an 8-byte aligned
+    destination)."""
+    import torch
+    lower = np.ascontiguousarray(schema[0], dtype=np.float32)
+    upper = np.ascontiguousarray(schema[1], dtype=np.float32)
+    K = len(lower)
+    h = abi.HistColumns(K, lower.ctypes.data, upper.ctypes.data, None)
+    dev = draw.t["qual"].device
+    offsets = torch.zeros(n_series + 1, dtype=torch.int64, device=dev)
+    raw = draw.as_abi()
+
+    def call(ts, cnt, cap):
+        engine._check(engine.lib.otsdb_hist_decode_rows_device(
+            engine.ctx, C.byref(raw), int(codec_id), n_series, C.byref(h),
+            offsets.data_ptr(), None if ts is None else ts.data_ptr(),
+            None if cnt is None else cnt.data_ptr(), cap, _stream(stream)))
+    call(None, None, 0)
+    n = int(offsets[-1].item())
+    cap = max(n, 2)  # (never an empty allocation: the pointers must be real)
+    ts = torch.zeros(cap, dtype=torch.int64, device=dev)
+    flat = torch.zeros(cap * (K + 2) + counts_offset + 2, dtype=torch.int64,
+                       device=dev)
+    cnt = flat[counts_offset:counts_offset + cap * (K + 2)].view(cap, K + 2)
+    call(ts, cnt, n)
+    return offsets, ts[:n], cnt[:n]

@@ -13,6 +13,10 @@ query's bucket schema; this module builds both from the sparse
                       the last two columns, 0 where a histogram lacks a key
   percentile_spec     the percentiles as the reference holds them: floats
                       (HistogramDataPointsToDataPointsAdaptor.percentile)
+  encode_simple, hist_qualifier, hist_rows
+                      the stored form: a histogram's value bytes, its
+                      qualifier, and the storage rows of a set of series
+                      (what otsdb_hist_run_rows decodes on the device)
 
 A key a histogram lacks is padded with 0: a zero-count key never qualifies
 for a percentile (its area is its predecessor's, or +-0.0 / NaN at the start),
@@ -158,3 +162,83 @@ class HistColumns:
                                self.upper.ctypes.data,
                                self.counts.ctypes.data
                                if self.counts.size else None)
+
+
+# ------------------------------------------------- stored form (storage rows)
+# What TSDB.addHistogramPoint writes and otsdb_hist_run_rows reads: the
+# qualifier of Internal.getQualifier with HistogramDataPoint.PREFIX and the
+# value of SimpleHistogram.histogram(true) through Kryo 3.0.0's Output.
+HIST_PREFIX = 0x06
+MAX_TIMESPAN = 3600
+SECOND_MASK = 0xFFFFFFFF00000000
+
+
+def write_var_long(v):
+    """Output.writeLong(v, true): 7 value bits a byte from the least
+    significant group, bit 7 set while more follow, the ninth byte whole."""
+    v &= (1 << 64) - 1
+    out = bytearray()
+    for _ in range(8):
+        if v >> 7 == 0:
+            out.append(v)
+            return bytes(out)
+        out.append((v & 0x7F) | 0x80)
+        v >>= 7
+    out.append(v)
+    return bytes(out)
+
+
+def encode_simple(hist, codec_id):
+    """The value bytes of `hist` (a Histogram) as
+    SimpleHistogram.histogram(true) writes them: the codec id, the short
+    bucket count, each key in TreeMap order as two big-endian floats and the
+    var-long count, then the var-long underflow and overflow.  (A histogram
+    without buckets whose underflow and overflow take one byte each is 5
+    bytes: fromHistogram refuses anything under 6, so it is never read
+    back.)"""
+    keys = sorted(hist.buckets)
+    out = bytearray([codec_id & 0xFF])
+    out += (len(keys) & 0xFFFF).to_bytes(2, "big")
+    for k in keys:
+        out += np.array([k.lower, k.upper], ">f4").tobytes()
+        out += write_var_long(hist.buckets[k])
+    out += write_var_long(hist.underflow)
+    out += write_var_long(hist.overflow)
+    return bytes(out)
+
+
+def hist_qualifier(ts, ms=None):
+    """Internal.getQualifier(ts, 0x06) -> (base_s, qualifier): `ts` in
+    seconds or, past 32 bits, in milliseconds as the reference tells them
+    apart (ms: say so instead).  A second timestamp gives the 3-byte form
+    (a short offset), a millisecond one the 5-byte form (an int offset)."""
+    ts = int(ts)
+    if ts < 1:
+        raise IllegalArgumentException("The start timestamp has not been set")
+    if ms is None:
+        ms = (ts & SECOND_MASK) != 0
+    if ms:
+        base = ts // 1000 - (ts // 1000) % MAX_TIMESPAN
+        return base, bytes([HIST_PREFIX]) + (ts - base * 1000).to_bytes(4, "big")
+    base = ts - ts % MAX_TIMESPAN
+    return base, bytes([HIST_PREFIX]) + (ts - base).to_bytes(2, "big")
+
+
+def hist_rows(series_points, codec_id):
+    """storage.HostRawRows of the series' histograms: series_points[s] is
+    [(ts_ms, Histogram)] in time order, one row per (series, base hour), one
+    cell per point — a whole-second timestamp with the 3-byte qualifier, any
+    other with the 5-byte one."""
+    from .storage import HostRawRows
+    rows = []
+    for s, pts in enumerate(series_points):
+        for ts, h in pts:
+            ts = int(ts)
+            base, q = (hist_qualifier(ts // 1000, ms=False) if ts % 1000 == 0
+                       else hist_qualifier(ts, ms=True))
+            if not rows or rows[-1][0] != s or rows[-1][1] != base:
+                rows.append((s, base, []))
+            rows[-1][2].append((q, encode_simple(h, codec_id)))
+    rr = HostRawRows(rows, with_ts=False)
+    rr.n_series = len(series_points)
+    return rr
