@@ -278,8 +278,6 @@ double pct_of(int agg) {  // PercentileAgg(percentile).evaluate(): p / 100d
   return P[(agg - OTSDB_AGG_P999) % 6] / 100.0;
 }
 
-constexpr int64_t kChunk = 256;  // series per cross-series chunk
-
 // k_keys_transpose's grid: KT_M members x OTSDB_KT_SLICES bucket slices
 dim3 kt_grid(int64_t M, int64_t NB) {
   const int64_t ntb = (NB + 63) / 64;
@@ -508,10 +506,8 @@ otsdb_status plan_anchored(const otsdb_query_spec* s, AnchoredPlan* A) {
   return check_spec(&A->derived);
 }
 
-// sel_all: every group (even one without local members) joins the radix
-// select lists — the cross-rank selection protocol needs global segments
-// whole_upto: groups of at most this many members are one tile (one
-// sequential chain), larger ones are cut into chunks of `chunk`
+// The groups' tiles on the device (the cut itself: foldplan.h, cut_tiles),
+// cached on its arguments
 otsdb_status build_tiles(otsdb_ctx* c, const std::vector<int64_t>& goff,
                          bool sel_all = false, int64_t chunk = kChunk,
                          int64_t whole_upto = 0) {
@@ -519,39 +515,15 @@ otsdb_status build_tiles(otsdb_ctx* c, const std::vector<int64_t>& goff,
       chunk == c->tiles_chunk && whole_upto == c->tiles_whole)
     return OTSDB_OK;
   const int64_t G = (int64_t)goff.size() - 1;
-  std::vector<int64_t> tg, tm0, tm1, mg, mt0, mt1, ag, at0, at1;
-  std::vector<int64_t> lgg, lgo, lgk, lgc{0};  // groups for radix select
-  std::vector<uint8_t> single;
-  for (int64_t g = 0; g < G; ++g) {
-    const int64_t a = goff[g], b = goff[g + 1];
-    const int64_t t0 = (int64_t)tg.size();
-    const int64_t ch = (b - a <= whole_upto) ? std::max<int64_t>(b - a, 1) : chunk;
-    for (int64_t m = a; m < b; m += ch) {
-      tg.push_back(g);
-      tm0.push_back(m);
-      tm1.push_back(std::min(b, m + ch));
-    }
-    const int64_t t1 = (int64_t)tg.size();
-    for (int64_t t = t0; t < t1; ++t) single.push_back(t1 - t0 == 1);
-    if (t1 - t0 > 1) {
-      mg.push_back(g);
-      mt0.push_back(t0);
-      mt1.push_back(t1);
-    }
-    ag.push_back(g);
-    at0.push_back(t0);
-    at1.push_back(t1);
-    if (b - a > SEL_K || sel_all) {
-      lgg.push_back(g);
-      lgo.push_back(a);
-      lgk.push_back(b - a);
-      lgc.push_back(lgc.back() + (b - a + SEL_CHUNK - 1) / SEL_CHUNK);
-    }
-  }
+  const TileCut tc = cut_tiles(goff, sel_all, chunk, whole_upto, SEL_K, SEL_CHUNK);
+  const auto &tg = tc.tg, &tm0 = tc.tm0, &tm1 = tc.tm1, &mg = tc.mg,
+             &mt0 = tc.mt0, &mt1 = tc.mt1, &ag = tc.ag, &at0 = tc.at0,
+             &at1 = tc.at1, &lgg = tc.lgg, &lgo = tc.lgo, &lgk = tc.lgk,
+             &lgc = tc.lgc;
+  const std::vector<uint8_t>& single = tc.single;
   const int64_t LG = (int64_t)lgg.size();
   const int64_t T = (int64_t)tg.size(), MG = (int64_t)mg.size();
-  int64_t max_chunks = 0;
-  for (int64_t k = 0; k < G; ++k) max_chunks = std::max(max_chunks, at1[k] - at0[k]);
+  const int64_t max_chunks = tc.max_chunks;
   // layout: tg tm0 tm1 [T] | mg mt0 mt1 [MG] | ag at0 at1 [G] |
   //         lg_g lg_off lg_k [LG] | lg_ch0 [LG+1] | single [T]
   const size_t n64 = 3 * T + 3 * MG + 3 * G + 4 * LG + 1;
@@ -628,20 +600,8 @@ Tiles tiles_of(otsdb_ctx* c, int64_t G) {
   return t;
 }
 
-// two-level ordered combine for groups of more than kCombineL1 chunks: the
-// single-level k_combine is one dependent chain of max_chunks loads per
-// (group, bucket) thread (C4: 1,953 chunks, 1.9 ms); first-level slices
-// cut it to ~max_chunks / kCombineSlices
-constexpr int64_t kCombineL1 = 128;
-constexpr int64_t kCombineSlices = 64;
-
-// whether n groups of up to max_chunks tiles combine in two levels (the
-// first-level slices within the budget), and the slices' buffers
-bool two_level_combine(int64_t max_chunks, int64_t n, int64_t NB) {
-  return max_chunks > kCombineL1 &&
-         (double)n * kCombineSlices * NB * 33.0 < 2.0e9;
-}
-
+// (kCombineL1, kCombineSlices and two_level_combine: foldplan.h)
+// the first-level slices' buffers
 void carve_combine(Carve& cv, Work& W, int64_t n_comb, int64_t NB) {
   W.comb = cv.take<Packed>((size_t)n_comb * kCombineSlices * NB);
   W.comb_emit = cv.take<uint8_t>((size_t)n_comb * kCombineSlices * NB);

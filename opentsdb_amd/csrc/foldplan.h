@@ -1,9 +1,11 @@
 // foldplan.h — how the ordered group fold (fold.hip, foldmulti.hip) is cut
 // into workgroups: the members of a tile, the buckets of a window and the
 // member contexts a tile preloads.  One (tile, window) pair is one workgroup,
-// so this plan decides the fold's speed and nothing of its results.  Host
-// code without a device header: the engine calls it for the single and the
-// multi-aggregator fold alike, tests/test_fold_plan_cpu.py compiles it alone.
+// so this plan decides the fold's speed and nothing of its results.  Also the
+// cut of every path's groups into tiles (cut_tiles) and the rule for the
+// two-level combine.  Host code without a device header: the engine calls it
+// for the single and the multi-aggregator fold alike, tests/test_fold_plan_
+// cpu.py and tests/test_group_shapes_cpu.py compile it alone.
 #pragma once
 #include <stdint.h>
 
@@ -61,6 +63,78 @@ struct FoldTiling {
 inline FoldTiling fold_tiling(bool ordered) {
   return ordered ? FoldTiling{kFoldChunk, kOrderedFoldChunk}
                  : FoldTiling{kFoldChunkLarge, kFoldChunk};
+}
+
+// series per cross-series chunk of the row path (k_group)
+constexpr int64_t kChunk = 256;
+
+// two-level ordered combine for groups of more than kCombineL1 chunks: the
+// single-level k_combine is one dependent chain of max_chunks loads per
+// (group, bucket) thread (C4: 1,953 chunks, 1.9 ms); first-level slices
+// cut it to ~max_chunks / kCombineSlices
+constexpr int64_t kCombineL1 = 128;
+constexpr int64_t kCombineSlices = 64;
+
+// whether n groups of up to max_chunks tiles combine in two levels (the
+// first-level slices within the budget)
+inline bool two_level_combine(int64_t max_chunks, int64_t n, int64_t NB) {
+  return max_chunks > kCombineL1 &&
+         (double)n * kCombineSlices * NB * 33.0 < 2.0e9;
+}
+
+// The cut of the groups into tiles, as the kernels read it (the engine's
+// build_tiles copies it to the device): tile t holds members [tm0, tm1) of
+// group tg and `single` says it is its group's only one; mg / mt0 / mt1 are
+// the groups of several tiles (k_combine's work), ag / at0 / at1 every
+// group's tile range (a group without members has none); lg_* the groups
+// for the radix select and their k_xsel_scan chunks.
+struct TileCut {
+  std::vector<int64_t> tg, tm0, tm1, mg, mt0, mt1, ag, at0, at1;
+  std::vector<int64_t> lgg, lgo, lgk, lgc{0};
+  std::vector<uint8_t> single;
+  int64_t max_chunks = 0;
+};
+
+// sel_all: every group (even one without local members) joins the radix
+// select lists — the cross-rank selection protocol needs global segments
+// whole_upto: groups of at most this many members are one tile (one
+// sequential chain), larger ones are cut into chunks of `chunk`
+// sel_k: groups of more members than the LDS sort holds (kernels.hip: SEL_K)
+// go to the radix select, in chunks of sel_chunk keys (select.hip: SEL_CHUNK)
+inline TileCut cut_tiles(const std::vector<int64_t>& goff, bool sel_all,
+                         int64_t chunk, int64_t whole_upto, int64_t sel_k,
+                         int64_t sel_chunk) {
+  TileCut c;
+  const int64_t G = (int64_t)goff.size() - 1;
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t a = goff[g], b = goff[g + 1];
+    const int64_t t0 = (int64_t)c.tg.size();
+    const int64_t ch = (b - a <= whole_upto) ? std::max<int64_t>(b - a, 1) : chunk;
+    for (int64_t m = a; m < b; m += ch) {
+      c.tg.push_back(g);
+      c.tm0.push_back(m);
+      c.tm1.push_back(std::min(b, m + ch));
+    }
+    const int64_t t1 = (int64_t)c.tg.size();
+    for (int64_t t = t0; t < t1; ++t) c.single.push_back(t1 - t0 == 1);
+    if (t1 - t0 > 1) {
+      c.mg.push_back(g);
+      c.mt0.push_back(t0);
+      c.mt1.push_back(t1);
+    }
+    c.ag.push_back(g);
+    c.at0.push_back(t0);
+    c.at1.push_back(t1);
+    if (b - a > sel_k || sel_all) {
+      c.lgg.push_back(g);
+      c.lgo.push_back(a);
+      c.lgk.push_back(b - a);
+      c.lgc.push_back(c.lgc.back() + (b - a + sel_chunk - 1) / sel_chunk);
+    }
+  }
+  for (int64_t k = 0; k < G; ++k)
+    c.max_chunks = std::max(c.max_chunks, c.at1[k] - c.at0[k]);
+  return c;
 }
 
 struct FoldPlan {

@@ -516,9 +516,12 @@ def test_big_groups_chunked(engine):
 
 
 def test_huge_group_two_level_combine(engine):
-    """One group of > 128 chunks (36k series): the ordered two-level chunk
-    combine (k_combine_l1 + k_combine) — exact for order-free aggregators,
-    1e-12 otherwise."""
+    """One group of 36,000 series: 4,500 fold tiles of 8 members, or 141
+    row-path chunks of 256 — either way past the 128 pieces (kCombineL1) at
+    which the ordered combine goes two-level (k_combine_l1 + k_combine; on
+    the fold that is from 1,025 members on, tests/test_gpu_group_shapes.py
+    sits on both sides of it) — exact for order-free aggregators, 1e-12
+    otherwise."""
     b = datasets.random_batch(73, n_series=36000, big_group=True,
                               span_ms=600 * 1000, cadence_ms=30000,
                               empty_frac=0.01)

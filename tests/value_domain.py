@@ -43,8 +43,9 @@ def base_batch(grouping, seed=301):
     """a: 40 series in 3 groups (each at most SEL_K = 32 members: LDS-sort
     select, one fold chunk); b: one group of 300 (k_seg_select's direct
     gather, chunk merges); c: one group of 1,100, all of them in the window
-    (more than SS_CAP = 1,024 candidates a bucket: the digit passes; 5
-    chunks); f: 300 series in 2 groups, both large (the FILL transpose)."""
+    (more than SS_CAP = 1,024 candidates a bucket: the digit passes; 138
+    fold tiles of 8 members, past the 128 of the two-level combine, or 5
+    row-path chunks of 256); f: 300 series in 2 groups, both large (the FILL transpose)."""
     kw = dict(span_ms=SPAN, cadence_ms=20_000)
     if grouping == "a":
         return datasets.random_batch(seed, n_series=40, n_groups=3, **kw)
