@@ -1124,6 +1124,125 @@ otsdb_status otsdb_hist_run_rows(otsdb_ctx* ctx, const otsdb_query_spec* spec,
                                  const float* percentiles, int32_t n_pct,
                                  otsdb_hist_result* out);
 
+/* ---- top-N over query results: highestMax / highestCurrent --------------- */
+/* The gexp functions highestMax(query, N) and highestCurrent(query, N)
+ * (src/query/expression/HighestMax.java:40-148, HighestCurrent.java:40-152)
+ * over the results of one or more sub-queries, each an otsdb_result as the
+ * query entries above write it: the answer is N series, not every group.
+ *
+ * The series are numbered in list order, then group order; highestMax numbers
+ * every series, highestCurrent drops the series without a point first
+ * (HighestCurrent.java:95-102).  n = the count.  Both functions run
+ * AggregationIterator(views, start_ms, end_ms, agg, LERP, rate = false) over
+ * the series (HighestMax.java:110-112): the seek goes to each series' first
+ * point >= start_ms; the emissions are the distinct timestamps <= end_ms of
+ * the points from there on; series i contributes at x iff it has a point
+ * after the seek and first_i <= x <= last_i, last_i its last point even past
+ * end_ms; its value is its own point or LERP between its neighbours
+ * (nextLongValue's wrapping, truncating long arithmetic on an integer
+ * emission, nextDoubleValue on a double one); an emission is integer iff no
+ * current or next slot of any series holds a double (a series not yet started
+ * shows its first point; AggregationIterator.java:612-625).
+ * The aggregator reads the values with nextLongValue / nextDoubleValue, which
+ * skip the series that do not contribute: the k-th CONTRIBUTING series' value
+ * lands in slot k, the rest of the n-vector is 0, and slot k's key is later
+ * taken as series k's key.  Reproduced.
+ *   highestMax (MaxCacheAggregator, HighestMax.java:182-292): max_longs[k]
+ *     from Long.MIN_VALUE, max_doubles[k] from Double.MIN_VALUE — the smallest
+ *     POSITIVE double, so all-negative double series tie at 4.9e-324; every
+ *     integer emission folds the whole vector with Math.max (the zero padding
+ *     counts), every double emission likewise (NaN is sticky, +0.0 over -0.0;
+ *     the padding never changes a slot there).
+ *   highestCurrent (MaxLatestAggregator, HighestCurrent.java:164-282):
+ *     latest_ts is never updated, so every emission overwrites: max_longs is
+ *     the whole vector (padding included) of the LAST integer emission,
+ *     max_doubles that of the LAST double emission.
+ * key[k]: both kinds of emission seen: Math.max((double)max_longs[k],
+ * max_doubles[k]); only integer ones: (double)max_longs[k]; only double ones:
+ * max_doubles[k].  The slots are sorted descending by Double.compare, stably
+ * (NaN first, ties in ascending k), and min(topn, n) series are returned:
+ * output i is the WHOLE point list of series k_i, points outside the window
+ * included, values and is_int untouched.
+ *
+ * Statuses: topn < 1, an unknown function, start_ms < 0: OTSDB_E_ILLEGAL_
+ * ARGUMENT; n == 0: OTSDB_OK, nothing picked; an x1 with millisecond-mask bits
+ * during LERP: the raw path's OTSDB_E_ILLEGAL_STATE.  Deviations: n > 0 with
+ * no emission in the window ends the reference in a NullPointerException
+ * (Arrays.sort over null entries, HighestMax.java:139): OTSDB_E_ILLEGAL_STATE
+ * here — a deviation in kind; a series whose timestamps do not strictly
+ * increase: OTSDB_E_UNSUPPORTED (the results of the query entries never hold
+ * one); end_ms >= 2^47, 2^31 series or 2^32 points: OTSDB_E_UNSUPPORTED.
+ *
+ * grid_interval_ms: the caller's promise that every timestamp of every input
+ * point is a multiple of it (every fixed-interval downsampled result), 0 for
+ * no promise.  It selects a path, never a result.  With a promise, a window
+ * of at most 65,536 grid timestamps and every point a double the call takes
+ * the grid path: no sort, no copy of the points, one synchronisation.  A
+ * promise that does not hold (an off-grid timestamp, a long, timestamps that
+ * do not increase) is found on the device and the general path runs in the
+ * same call — as every call without a promise does (any input; O(emissions x
+ * series x log points), four synchronisations).  The two are bit-identical
+ * wherever both apply.
+ * otsdb_ctx_counters [18..20], of the last top-N call: [18] 1 when the grid
+ * path was run, [19] 1 when the general path was run, [20] 1 when the grid
+ * path's promise did not hold (then [18] = [19] = 1).                        */
+typedef enum {
+  OTSDB_TOPN_HIGHEST_MAX = 0,     /* "highestMax"     */
+  OTSDB_TOPN_HIGHEST_CURRENT = 1  /* "highestCurrent" */
+} otsdb_topn_function;
+
+typedef struct {
+  int32_t function;          /* otsdb_topn_function                          */
+  int32_t topn;              /* N                                            */
+  int64_t start_ms;          /* TSQuery.startTime()                          */
+  int64_t end_ms;            /* TSQuery.endTime()                            */
+  int64_t grid_interval_ms;  /* see above; 0 = no promise                    */
+} otsdb_topn_spec;
+
+/* n_out = min(topn, series of every input).  `series`: the picked series in
+ * rank order, offsets [n_out + 1] (series i's points are [offsets[i],
+ * offsets[i + 1])), ts / val / is_int [capacity]; DEVICE pointers for
+ * otsdb_topn_run_device, HOST pointers for otsdb_topn_run.  picked / key:
+ * HOST memory on both entries, [n_out] each (NULL skips one): picked[i] is
+ * output i's series number in the input's flat numbering — highestMax's,
+ * empty series counted, for both functions — and key[i] its key as double
+ * bits, NaN canonical (0x7FF8000000000000).  n_picked: outputs written.      */
+typedef struct {
+  otsdb_result series;
+  int64_t* picked;
+  int64_t* key;
+  int64_t n_picked;
+} otsdb_topn_result;
+
+/* Sizes from the inputs' shapes (HOST arrays of n_results entries; no device
+ * work, ctx is not read): n_buckets = n_out above, max_out_points = the points
+ * of every input (what the n_out longest series can hold at most),
+ * workspace_bytes the general path's device scratch (an upper estimate: 17 B
+ * a point of columnar view, 24 B of keys, the sorts' own scratch; ~180 B a
+ * series).  The spec's checks.                                               */
+otsdb_status otsdb_topn_plan(otsdb_ctx* ctx, const otsdb_topn_spec* spec,
+                             int32_t n_results, const int64_t* n_groups,
+                             const int64_t* n_points, otsdb_sizes* out);
+/* results: HOST array of n_results structs with DEVICE pointers inside (what
+ * otsdb_agg_run_device and its kin wrote; capacity is not read), n_groups
+ * (HOST) each one's group count.  Runs on hip_stream (NULL: the context's)
+ * and returns after the result is complete on the device and picked / key /
+ * n_picked on the host (the kernels write them to mapped host memory, the
+ * pattern of the compaction's {error word, total}: no read-back copies).  A capacity too small: OTSDB_E_CAPACITY with
+ * series.offsets, picked, key and n_picked whole (offsets[n_picked] is the
+ * capacity a retry needs).  Replaces HighestMax.evaluate /
+ * HighestCurrent.evaluate over the DataPoints[] of the sub-queries.          */
+otsdb_status otsdb_topn_run_device(otsdb_ctx* ctx, const otsdb_topn_spec* spec,
+                                   int32_t n_results,
+                                   const otsdb_result* results,
+                                   const int64_t* n_groups,
+                                   otsdb_topn_result* out, void* hip_stream);
+/* Host pointers throughout (the JNI entry at the gexp seam,
+ * HighestMax.java:40-41); synchronous; the same OTSDB_E_CAPACITY contract.   */
+otsdb_status otsdb_topn_run(otsdb_ctx* ctx, const otsdb_topn_spec* spec,
+                            int32_t n_results, const otsdb_result* results,
+                            const int64_t* n_groups, otsdb_topn_result* out);
+
 /* ---- stage timing (bench roofline) ------------------------------------- */
 /* When enabled, every query records HIP events around its pipeline stages
  * on the query's stream.  otsdb_prof_read returns, per stage, the summed
@@ -1133,7 +1252,8 @@ otsdb_status otsdb_hist_run_rows(otsdb_ctx* ctx, const otsdb_query_spec* spec,
  * decode into the context's columnar buffer (compacted cells, rollup rows);
  * histogram queries: [8] k_hist_prep + k_hist_fold, [9] k_hist_combine,
  * [10] k_hist_percentiles, [11] their compaction; [12] the decode of
- * histogram storage rows (otsdb_hist_run_rows*) (n up to 13).
+ * histogram storage rows (otsdb_hist_run_rows*); [13] a top-N call
+ * (otsdb_topn_run*: numbering to gather) (n up to 14).
  * Synchronises the stream.                                                  */
 otsdb_status otsdb_prof_enable(otsdb_ctx* ctx, int enable);
 otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
@@ -1161,7 +1281,9 @@ otsdb_status otsdb_prof_read(otsdb_ctx* ctx, double* ms, int64_t* launches,
  * passes over the dense sums (1, or 0 when n_pct == 0).  Of the last
  * otsdb_hist_*rows* call: out[15] histogram cells decoded into points,
  * out[16] cells skipped as undecodable, out[17] points dropped by a same-key
- * merge.                                                                    */
+ * merge.  Of the last otsdb_topn_* call: out[18] runs of the grid path,
+ * out[19] runs of the general path, out[20] grid promises missed (the general
+ * path then ran again).                                                     */
 otsdb_status otsdb_ctx_counters(otsdb_ctx* ctx, int64_t* out, int n);
 /* Test hook: the one-pass compaction's epoch (1 .. 2^24 - 1, forward only)
  * the context's next call increments, so tests can drive it to its wrap.  */

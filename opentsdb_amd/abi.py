@@ -153,6 +153,31 @@ class HistResult(C.Structure):
     ]
 
 
+class TopNSpec(C.Structure):
+    """otsdb_topn_spec."""
+    _fields_ = [
+        ("function", C.c_int32),
+        ("topn", C.c_int32),
+        ("start_ms", C.c_int64),
+        ("end_ms", C.c_int64),
+        ("grid_interval_ms", C.c_int64),
+    ]
+
+
+class TopNResult(C.Structure):
+    """otsdb_topn_result: the picked series (an otsdb_result, offsets
+    [n_out + 1]), then host arrays picked / key [n_out] and n_picked."""
+    _fields_ = [
+        ("series", Result),
+        ("picked", C.c_void_p),
+        ("key", C.c_void_p),
+        ("n_picked", C.c_int64),
+    ]
+
+
+TOPN_HIGHEST_MAX = 0      # otsdb_topn_function
+TOPN_HIGHEST_CURRENT = 1
+
 HIST_MAX_ROW = 256  # OTSDB_HIST_MAX_ROW
 HIST_MAX_PCT = 16   # OTSDB_HIST_MAX_PCT
 
@@ -202,6 +227,7 @@ EXPORTS = [
     "otsdb_hist_window",
     "otsdb_hist_rows_schema_device", "otsdb_hist_decode_rows_device",
     "otsdb_hist_run_rows_device", "otsdb_hist_run_rows",
+    "otsdb_topn_plan", "otsdb_topn_run_device", "otsdb_topn_run",
 ]
 
 MULTI_MAX = 32  # OTSDB_MULTI_MAX
@@ -392,6 +418,17 @@ def load(path=None):
         lib.otsdb_hist_run_rows.argtypes = [vp, PS, PW, i32, PB, PH, vp, i32,
                                             PHR]
         lib.otsdb_hist_run_rows.restype = C.c_int
+    # top-N over query results: (ctx, spec, n_results, n_groups, n_points,
+    # sizes) and (ctx, spec, n_results, results[n_results], n_groups, result
+    # [, stream])
+    if hasattr(lib, "otsdb_topn_run"):
+        PTS, PTR = C.POINTER(TopNSpec), C.POINTER(TopNResult)
+        lib.otsdb_topn_plan.argtypes = [vp, PTS, i32, vp, vp, C.POINTER(Sizes)]
+        lib.otsdb_topn_plan.restype = C.c_int
+        lib.otsdb_topn_run_device.argtypes = [vp, PTS, i32, PR, vp, PTR, vp]
+        lib.otsdb_topn_run_device.restype = C.c_int
+        lib.otsdb_topn_run.argtypes = [vp, PTS, i32, PR, vp, PTR]
+        lib.otsdb_topn_run.restype = C.c_int
     # bound only on the ABI it was added to: a stale library of another
     # version must not hand out a symbol of other arguments
     if lib.otsdb_abi_version() == 6 and hasattr(lib, "otsdb_sel_retarget"):

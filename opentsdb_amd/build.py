@@ -54,7 +54,7 @@ _DS = ("ds_tu.hip", "decode.hip", "fold.hip", "foldmulti.hip",
 UNIT_FILES = {
     "engine": ("engine.hip", "engine_int.h", "compact.hip", "select.hip",
                "decode.hip", "raw.hip", "calendar.hip", "multi.hip",
-               "panel.hip", "foldplan.h", "menv.h") + _SHARED,
+               "panel.hip", "topn.hip", "foldplan.h", "menv.h") + _SHARED,
     "engine_rows": ("engine_rows.hip", "engine_int.h", "decode.hip",
                     "rows.hip", "rollup_rows.hip") + _SHARED,
     "engine_hist": ("engine_hist.hip", "engine_int.h", "compact.hip",

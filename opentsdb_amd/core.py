@@ -459,3 +459,59 @@ def make_spec(start_time, end_time, aggregator, downsampler=None,
     s.counter_max = ro.counter_max
     s.reset_value = ro.reset_value
     return s
+
+
+# ------------------------------------------------- gexp top-N functions
+TOPN_FUNCTIONS = {"highestMax": 0, "highestCurrent": 1}  # otsdb_topn_function
+
+
+def topn_function(name):
+    """The otsdb_topn_function id of a gexp function name
+    (ExpressionFactory registers "highestMax" and "highestCurrent"; names are
+    case sensitive).  An id passes through."""
+    if isinstance(name, int) and name in TOPN_FUNCTIONS.values():
+        return int(name)
+    try:
+        return TOPN_FUNCTIONS[name]
+    except (KeyError, TypeError):
+        raise IllegalArgumentException("No top-N function: %r" % (name,))
+
+
+def parse_topn(params):
+    """The top-n parameter of highestMax / highestCurrent
+    (HighestMax.java:49-73): `params` is the function's parameter list; its
+    first entry must match ^[0-9]+$, parse as a Java int
+    (Integer.parseInt: above 2^31 - 1 is a NumberFormatException) and be at
+    least 1.  Everything else is an IllegalArgumentException."""
+    if params is None or len(params) == 0:
+        raise IllegalArgumentException(
+            "Need aggregation window for moving average")
+    param = params[0]
+    if param is None or (isinstance(param, str) and len(param) == 0):
+        raise IllegalArgumentException(
+            "Missing top n value (number of series to return)")
+    if not isinstance(param, str) or not all("0" <= ch <= "9" for ch in param):
+        raise IllegalArgumentException("Unparseable top n value: %s" % (param,))
+    topn = int(param)
+    if topn > 2 ** 31 - 1:
+        raise IllegalArgumentException("Invalid parameter, must be an integer")
+    if topn < 1:
+        raise IllegalArgumentException(
+            "Top n value must be greater than zero: %d" % topn)
+    return topn
+
+
+def topn_grid_interval_ms(downsampler):
+    """otsdb_topn_spec.grid_interval_ms for the results of a query with this
+    DownsamplingSpecification (or its string, or None): the interval of a
+    fixed-interval downsampler, whose bucket timestamps are all multiples of
+    it; 0 (no promise) without a downsampler, for calendar intervals and for
+    "0all"."""
+    if downsampler is None:
+        return 0
+    if isinstance(downsampler, str):
+        downsampler = DownsamplingSpecification(downsampler)
+    if downsampler.run_all or downsampler.useCalendar():
+        return 0
+    iv = int(downsampler.getInterval())
+    return iv if iv > 0 else 0

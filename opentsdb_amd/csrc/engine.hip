@@ -26,8 +26,10 @@
 #include <type_traits>
 #include <vector>
 
+#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/device/device_select.hpp>
 
 #include "../../include/otsdb_agg.h"
 #include "kernels.hip"
@@ -38,6 +40,7 @@
 #include "calendar.hip"
 #include "multi.hip"
 #include "panel.hip"
+#include "topn.hip"
 #include "launch.h"
 #include "foldplan.h"
 #include "engine_int.h"
@@ -3472,6 +3475,425 @@ otsdb_status run_cells_impl(otsdb_ctx* c, const otsdb_query_spec* spec,
 }  // namespace otsdb
 
 // =========================================================================
+// Top-N over query results (topn.hip): highestMax / highestCurrent
+// =========================================================================
+namespace {
+
+otsdb_status check_topn(const otsdb_topn_spec* ts, int32_t n_results,
+                        const otsdb_result* results, const int64_t* n_groups,
+                        int64_t* n_series) {
+  if (ts->function != OTSDB_TOPN_HIGHEST_MAX &&
+      ts->function != OTSDB_TOPN_HIGHEST_CURRENT)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "no top-N function %d", ts->function);
+  if (ts->topn < 1)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT,
+                "Top n value must be greater than zero: %d", ts->topn);
+  if (ts->start_ms < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative start");
+  if (ts->grid_interval_ms < 0)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "negative grid interval");
+  if (n_results < 0 || (n_results > 0 && (!results || !n_groups)))
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null results");
+  int64_t S = 0;
+  for (int32_t r = 0; r < n_results; ++r) {
+    if (n_groups[r] < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "n_groups < 0");
+    if (n_groups[r] > 0 && !results[r].offsets)
+      return fail(OTSDB_E_ILLEGAL_ARGUMENT, "result %d without offsets", r);
+    S += n_groups[r];
+  }
+  if (S >= ((int64_t)1 << 31))
+    return fail(OTSDB_E_UNSUPPORTED, "top-N over %lld series", (long long)S);
+  // emission keys carry the timestamp in 47 bits (raw.hip)
+  if (ts->end_ms >= kRawTsMax)
+    return fail(OTSDB_E_UNSUPPORTED, "top-N window past 2^47 ms");
+  *n_series = S;
+  return OTSDB_OK;
+}
+
+otsdb_status topn_status(int err) {
+  if (err & ERR_RAW_DUP)
+    return fail(OTSDB_E_UNSUPPORTED,
+                "top-N: a series' timestamps do not increase strictly (or a "
+                "window point lies past 2^47 ms)");
+  if (err & ERR_X1_MASK)
+    return fail(OTSDB_E_ILLEGAL_STATE, "x1 beyond the millisecond mask");
+  return OTSDB_OK;
+}
+
+// the mapped host block a top-N call reports through (topn.hip, TOPN_H_*)
+otsdb_status topn_host_block(otsdb_ctx* c, int64_t n_out) {
+  const size_t need = sizeof(int64_t) * (size_t)(TOPN_HDR + 2 * n_out);
+  if (need > c->topn_host_cap) {
+    if (c->h_topn) hipHostFree(c->h_topn);
+    c->h_topn = c->d_topn = nullptr;
+    c->topn_host_cap = 0;
+    const size_t cap = std::max(need, (size_t)4096);
+    HIP_TRY(hipHostMalloc(&c->h_topn, cap,
+                          hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(hipHostGetDevicePointer((void**)&c->d_topn, c->h_topn, 0));
+    c->topn_host_cap = cap;
+  }
+  for (int i = 0; i < TOPN_HDR; ++i) c->h_topn[i] = 0;
+  return OTSDB_OK;
+}
+
+// the per-series arrays both paths use (carved from c->ws)
+struct TopnWork {
+  TopnSrc* src;
+  int32_t *sres, *slot_in, *slot_out, *fb, *lb;
+  int64_t *sp0, *slen, *soff, *numbered, *nrank, *members, *lo, *hi, *keybits,
+      *picked, *pcount, *ccount, *coff;
+  long long *maxl, *marks;
+  unsigned long long* maxd;
+  uint64_t *sk_in, *sk_out;
+  int* flags;
+  size_t carve(char* base, int R, int64_t S) {
+    Carve cv{base};
+    src = cv.take<TopnSrc>(R);
+    sres = cv.take<int32_t>(S);
+    sp0 = cv.take<int64_t>(S);
+    slen = cv.take<int64_t>(S + 1);
+    soff = cv.take<int64_t>(S + 1);
+    numbered = cv.take<int64_t>(S + 1);
+    nrank = cv.take<int64_t>(S + 1);
+    members = cv.take<int64_t>(S);
+    lo = cv.take<int64_t>(S + 1);
+    hi = cv.take<int64_t>(S + 1);
+    fb = cv.take<int32_t>(S);
+    lb = cv.take<int32_t>(S);
+    maxl = cv.take<long long>(S);
+    maxd = cv.take<unsigned long long>(S);
+    marks = cv.take<long long>(TOPN_MARKS);
+    flags = cv.take<int>(4);
+    sk_in = cv.take<uint64_t>(S);
+    sk_out = cv.take<uint64_t>(S);
+    slot_in = cv.take<int32_t>(S);
+    slot_out = cv.take<int32_t>(S);
+    keybits = cv.take<int64_t>(S);
+    picked = cv.take<int64_t>(S);
+    pcount = cv.take<int64_t>(S + 1);
+    ccount = cv.take<int64_t>(S + 1);
+    coff = cv.take<int64_t>(S + 1);
+    return cv.off + 256;
+  }
+};
+
+// numbering: per series its result, place and count; the numbered series
+otsdb_status topn_number(otsdb_ctx* c, const otsdb_topn_spec* ts, int32_t R,
+                         const otsdb_result* res, const int64_t* n_groups,
+                         int64_t S, TopnWork& W) {
+  hipStream_t st = c->stream;
+  std::vector<TopnSrc> hs((size_t)R);
+  int64_t s0 = 0;
+  for (int32_t r = 0; r < R; ++r) {
+    hs[r] = TopnSrc{res[r].offsets, res[r].ts, res[r].val, res[r].is_int, s0};
+    s0 += n_groups[r];
+  }
+  otsdb_status rc = c->ws.ensure(W.carve(nullptr, R, S));
+  if (rc) return rc;
+  W.carve((char*)c->ws.p, R, S);
+  // (pageable source: the copy is staged before the call returns)
+  HIP_TRY(hipMemcpyAsync(W.src, hs.data(), sizeof(TopnSrc) * (size_t)R,
+                         hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(c->d_err, 0, sizeof(int), st));
+  HIP_TRY(hipMemsetAsync(W.flags, 0, sizeof(int) * 4, st));
+  hipLaunchKernelGGL(k_topn_series, dim3(blocks_for(S, 256)), dim3(256), 0, st,
+                     (int)R, (const TopnSrc*)W.src, S, (int)ts->function, W.sres,
+                     W.sp0, W.slen, W.numbered);
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, S,
+                     (const int64_t*)W.slen, W.soff);
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, S,
+                     (const int64_t*)W.numbered, W.nrank);
+  hipLaunchKernelGGL(k_topn_members, dim3(blocks_for(S, 256)), dim3(256), 0, st,
+                     S, (const int64_t*)W.numbered, (const int64_t*)W.nrank,
+                     W.members);
+  hipLaunchKernelGGL(k_topn_init, dim3(blocks_for(S, 256)), dim3(256), 0, st, S,
+                     W.maxl, W.maxd, W.marks);
+  HIP_TRY(hipGetLastError());
+  return OTSDB_OK;
+}
+
+// keys -> stable sort -> pick -> offsets -> report -> gather; ONE
+// synchronisation, then picked / key / n_picked from the mapped block.
+// Returns with c->h_topn read; the status of the call's end.
+otsdb_status topn_select(otsdb_ctx* c, const otsdb_topn_spec* ts, int64_t S,
+                         TopnWork& W, bool grid, otsdb_topn_result* out) {
+  hipStream_t st = c->stream;
+  const int fn = ts->function;
+  const int64_t n_out = std::min<int64_t>(ts->topn, S);
+  const int64_t* n_dev = W.nrank + S;
+  size_t t_pairs = 0;
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, t_pairs, (const uint64_t*)nullptr,
+                                    (uint64_t*)nullptr, (const int32_t*)nullptr,
+                                    (int32_t*)nullptr, (size_t)S, 0u, 64u, st));
+  // (the general path's sorts are done with this buffer: stream order)
+  otsdb_status rc = c->dec_ws.ensure(t_pairs + 256);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_topn_keys, dim3(blocks_for(S, 256)), dim3(256), 0, st, fn,
+                     S, n_dev, (const long long*)W.marks,
+                     (const long long*)W.maxl,
+                     (const unsigned long long*)W.maxd, W.sk_in, W.keybits,
+                     W.slot_in);
+  HIP_TRY(rocprim::radix_sort_pairs(c->dec_ws.p, t_pairs,
+                                    (const uint64_t*)W.sk_in, W.sk_out,
+                                    (const int32_t*)W.slot_in, W.slot_out,
+                                    (size_t)S, 0u, 64u, st));
+  hipLaunchKernelGGL(k_topn_pick, dim3(blocks_for(n_out, 256)), dim3(256), 0, st,
+                     n_out, (int64_t)ts->topn, n_dev,
+                     (const int32_t*)W.slot_out, (const int64_t*)W.keybits,
+                     (const int64_t*)W.members, (const int64_t*)W.slen,
+                     W.picked, W.pcount, c->d_topn);
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, n_out,
+                     (const int64_t*)W.pcount, out->series.offsets);
+  hipLaunchKernelGGL(k_topn_done, dim3(1), dim3(64), 0, st, n_out,
+                     (const int64_t*)out->series.offsets, (const int*)c->d_err,
+                     (const int*)W.flags, (const long long*)W.marks, c->d_topn);
+  // (a series that does not fit the capacity is not copied)
+  hipLaunchKernelGGL(k_topn_gather, dim3(blocks_for(n_out, 4)), dim3(256), 0, st,
+                     n_out, (const int64_t*)W.picked, (const TopnSrc*)W.src,
+                     (const int32_t*)W.sres, (const int64_t*)W.sp0,
+                     (const int64_t*)out->series.offsets, out->series.capacity,
+                     out->series.ts, out->series.val, out->series.is_int);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t* H = c->h_topn;
+  const int flags = (int)__atomic_load_n(&H[TOPN_H_FLAGS], __ATOMIC_ACQUIRE);
+  if (grid && (flags & TOPN_F_MISS)) return OTSDB_OK;  // the caller re-runs
+  if ((rc = topn_status((int)H[TOPN_H_ERR]))) return rc;
+  if (H[TOPN_H_N] == 0) {  // nothing numbered: nothing picked
+    out->n_picked = 0;
+    return OTSDB_OK;
+  }
+  if (!(flags & TOPN_F_EMITTED))
+    return fail(OTSDB_E_ILLEGAL_STATE,
+                "top-N: no data point inside the window (the reference ends "
+                "in a NullPointerException, HighestMax.java:139)");
+  const int64_t k = H[TOPN_H_NPICK];
+  if (out->picked) memcpy(out->picked, H + TOPN_HDR, 8 * (size_t)k);
+  if (out->key) memcpy(out->key, H + TOPN_HDR + n_out, 8 * (size_t)k);
+  out->n_picked = k;
+  c->h_small[1] = H[TOPN_H_TOTAL];
+  if (H[TOPN_H_TOTAL] > out->series.capacity) {
+    c->result_short = true;
+    return fail(OTSDB_E_CAPACITY, "result capacity %lld < %lld points",
+                (long long)out->series.capacity, (long long)H[TOPN_H_TOTAL]);
+  }
+  return OTSDB_OK;
+}
+
+// The general path (topn.hip): any input.  Three synchronisations before the
+// last (the point count, the candidate count, the emission count).
+otsdb_status topn_general(otsdb_ctx* c, const otsdb_topn_spec* ts, int64_t S,
+                          TopnWork& W, otsdb_topn_result* out) {
+  hipStream_t st = c->stream;
+  const int fn = ts->function;
+  HIP_TRY(hipMemcpyAsync(&c->h_small[2], W.soff + S, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&c->h_small[3], W.nrank + S, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t N = c->h_small[2], n = c->h_small[3];
+  if (N >= ((int64_t)1 << 32))
+    return fail(OTSDB_E_UNSUPPORTED, "top-N (general path) over %lld points",
+                (long long)N);
+  int64_t E = 0;
+  if (n > 0) {
+    const int end_bit =
+        kOccBits +
+        std::max(1, 64 - __builtin_clzll((uint64_t)std::max<int64_t>(ts->end_ms, 1)));
+    int64_t *cts, *cval;
+    uint8_t* cflt;
+    uint64_t *kin, *kout, *kuniq;
+    unsigned long long* d_cnt;
+    auto carve2 = [&](char* base) {
+      Carve cv{base};
+      cts = cv.take<int64_t>(N + 1);
+      cval = cv.take<int64_t>(N + 1);
+      cflt = cv.take<uint8_t>(N + 1);
+      kin = cv.take<uint64_t>(N + 1);
+      kout = cv.take<uint64_t>(N + 1);
+      kuniq = cv.take<uint64_t>(N + 1);
+      d_cnt = cv.take<unsigned long long>(1);
+      return cv.off + 256;
+    };
+    otsdb_status rc = c->ws2.ensure(carve2(nullptr));
+    if (rc) return rc;
+    carve2((char*)c->ws2.p);
+    hipLaunchKernelGGL(k_topn_concat, dim3(blocks_for(S, 4)), dim3(256), 0, st,
+                       S, ts->start_ms, (const TopnSrc*)W.src,
+                       (const int32_t*)W.sres, (const int64_t*)W.sp0,
+                       (const int64_t*)W.soff, cts, cval, cflt, W.lo, W.hi,
+                       W.marks, c->d_err);
+    Params P{};
+    P.start_ms = ts->start_ms;
+    P.end_ms = ts->end_ms;
+    P.interp = OTSDB_INTERP_LERP;
+    RawView V;
+    V.ts = cts;
+    V.val = cval;
+    V.is_float = cflt;
+    V.series_float = nullptr;
+    V.all_double = 0;
+    V.lo = W.lo;
+    V.hi = W.hi;
+    hipLaunchKernelGGL(k_raw_cand_count, dim3(blocks_for(n, 256)), dim3(256), 0,
+                       st, P, V, n, (const int64_t*)W.members, W.ccount);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, n,
+                       (const int64_t*)W.ccount, W.coff);
+    HIP_TRY(hipMemcpyAsync(&c->h_small[2], W.coff + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t C = c->h_small[2];
+    if (C < 0 || C > N)
+      return fail(OTSDB_E_DEVICE, "internal: %lld candidates", (long long)C);
+    if (C > 0) {
+      // the device sorts' scratch, sized for this call's C candidates
+      size_t t_sort = 0, t_uniq = 0;
+      HIP_TRY(rocprim::radix_sort_keys(nullptr, t_sort, (const uint64_t*)nullptr,
+                                       (uint64_t*)nullptr, (size_t)C, 0u,
+                                       (unsigned)end_bit, st));
+      HIP_TRY(rocprim::unique(nullptr, t_uniq, (const uint64_t*)nullptr,
+                              (uint64_t*)nullptr, (unsigned long long*)nullptr,
+                              (size_t)C, rocprim::equal_to<uint64_t>(), st));
+      const size_t tmp_bytes = std::max(t_sort, t_uniq) + 256;
+      rc = c->dec_ws.ensure(tmp_bytes);
+      if (rc) return rc;
+      void* tmp = c->dec_ws.p;
+      hipLaunchKernelGGL(k_raw_cand_fill, dim3(blocks_for(n, 4)), dim3(256), 0,
+                         st, P, V, n, (const int64_t*)W.members,
+                         (const int64_t*)W.coff, kin, c->d_err);
+      size_t tb = tmp_bytes;
+      HIP_TRY(rocprim::radix_sort_keys(tmp, tb, (const uint64_t*)kin, kout,
+                                       (size_t)C, 0u, (unsigned)end_bit, st));
+      tb = tmp_bytes;
+      HIP_TRY(rocprim::unique(tmp, tb, (const uint64_t*)kout, kuniq, d_cnt,
+                              (size_t)C, rocprim::equal_to<uint64_t>(), st));
+      HIP_TRY(hipMemcpyAsync(&c->h_small[2], d_cnt, 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      E = c->h_small[2];
+    }
+    if (E > 0) {
+      hipLaunchKernelGGL(k_topn_eval, dim3(blocks_for(E, 256)), dim3(256), 0, st,
+                         P, V, fn, n, (const int64_t*)W.members, E,
+                         (const uint64_t*)kuniq, W.maxl, W.maxd, W.marks,
+                         c->d_err);
+      if (fn == OTSDB_TOPN_HIGHEST_CURRENT)
+        hipLaunchKernelGGL(k_topn_current, dim3(2), dim3(kTopnRound), 0, st, P,
+                           V, n, (const int64_t*)W.members,
+                           (const uint64_t*)kuniq, (const long long*)W.marks,
+                           (int64_t*)W.maxl, (int64_t*)W.maxd, c->d_err);
+    }
+  }
+  return topn_select(c, ts, S, W, false, out);
+}
+
+// The grid path (topn.hip) applies: a promise, a window of at most
+// kTopnGridCap buckets, a count table under 1 GiB.
+bool topn_grid_plan(const otsdb_topn_spec* ts, int64_t S, TopnGrid* Q,
+                    int64_t* tiles) {
+  const int64_t iv = ts->grid_interval_ms;
+  if (iv <= 0 || ts->end_ms < ts->start_ms) return false;
+  const int64_t r = ts->start_ms % iv;
+  if (r && ts->start_ms > INT64_MAX - iv) return false;
+  Q->iv = iv;
+  Q->start_ms = ts->start_ms;
+  Q->gbase = r ? ts->start_ms + (iv - r) : ts->start_ms;
+  Q->NB = ts->end_ms >= Q->gbase ? (ts->end_ms - Q->gbase) / iv + 1 : 0;
+  if (Q->NB < 1 || Q->NB > kTopnGridCap) return false;
+  *tiles = (S + kTopnTile - 1) / kTopnTile;
+  return (double)*tiles * (double)(Q->NB + 1) * 4.0 <= (double)(1 << 30);
+}
+
+// Enqueues the whole grid path; *missed: the promise did not hold (nothing
+// of `out` is to be trusted; the general path runs).  One synchronisation.
+otsdb_status topn_grid(otsdb_ctx* c, const otsdb_topn_spec* ts, int64_t S,
+                       const TopnGrid& Q, int64_t tiles, TopnWork& W,
+                       otsdb_topn_result* out, bool* missed) {
+  hipStream_t st = c->stream;
+  const bool fmax = ts->function == OTSDB_TOPN_HIGHEST_MAX;
+  const int64_t words = (Q.NB + 63) / 64;
+  unsigned long long* bitmap;
+  int32_t* table = nullptr;
+  auto carve = [&](char* base) {
+    Carve cv{base};
+    bitmap = cv.take<unsigned long long>(words + 1);
+    if (fmax) table = cv.take<int32_t>(tiles * (Q.NB + 1));
+    return cv.off + 256;
+  };
+  otsdb_status rc = c->ws2.ensure(carve(nullptr));
+  if (rc) return rc;
+  const size_t bytes = carve((char*)c->ws2.p) - 256;
+  HIP_TRY(hipMemsetAsync(c->ws2.p, 0, bytes, st));
+  const int64_t* n_dev = W.nrank + S;
+  hipLaunchKernelGGL(k_topn_grid_scan, dim3(blocks_for(S, 4)), dim3(256), 0, st,
+                     Q, S, n_dev, (const int64_t*)W.members,
+                     (const TopnSrc*)W.src, (const int32_t*)W.sres,
+                     (const int64_t*)W.sp0, (const int64_t*)W.slen, bitmap,
+                     W.lo, W.fb, W.lb, table, W.flags);
+  hipLaunchKernelGGL(k_topn_grid_last, dim3(blocks_for(words, 256)), dim3(256),
+                     0, st, words, (const unsigned long long*)bitmap, W.marks);
+  if (fmax) {
+    hipLaunchKernelGGL(k_topn_grid_tiles, dim3(blocks_for(Q.NB + 1, 256)),
+                       dim3(256), 0, st, Q.NB, tiles, table);
+    hipLaunchKernelGGL(k_topn_grid_rows, dim3(blocks_for(tiles, 4)), dim3(256),
+                       0, st, Q.NB, tiles, table);
+    hipLaunchKernelGGL(k_topn_grid_max, dim3(blocks_for(S, 4)), dim3(256), 0, st,
+                       Q, S, n_dev, (const int64_t*)W.members,
+                       (const TopnSrc*)W.src, (const int32_t*)W.sres,
+                       (const int64_t*)W.sp0, (const int64_t*)W.slen,
+                       (const unsigned long long*)bitmap, (const int64_t*)W.lo,
+                       (const int32_t*)W.fb, (const int32_t*)W.lb,
+                       (const int32_t*)table, W.maxd, c->d_err);
+  } else {
+    hipLaunchKernelGGL(k_topn_grid_current, dim3(1), dim3(kTopnRound), 0, st, Q,
+                       n_dev, (const int64_t*)W.members, (const TopnSrc*)W.src,
+                       (const int32_t*)W.sres, (const int64_t*)W.sp0,
+                       (const int64_t*)W.slen, (const int64_t*)W.lo,
+                       (const int32_t*)W.fb, (const int32_t*)W.lb,
+                       (const long long*)W.marks, (int64_t*)W.maxd, c->d_err);
+  }
+  rc = topn_select(c, ts, S, W, true, out);
+  *missed = (c->h_topn[TOPN_H_FLAGS] & TOPN_F_MISS) != 0;
+  return rc;
+}
+
+// `res`: device pointers; out->series: device pointers; out->picked /
+// out->key: host.  The grid path where the caller's promise allows it (one
+// synchronisation), the general path otherwise or after a missed promise.
+otsdb_status run_topn_impl(otsdb_ctx* c, const otsdb_topn_spec* ts, int32_t R,
+                           const otsdb_result* res, const int64_t* n_groups,
+                           int64_t S, otsdb_topn_result* out) {
+  hipStream_t st = c->stream;
+  c->n_topn_grid = c->n_topn_general = c->n_topn_miss = 0;
+  out->n_picked = 0;
+  c->result_short = false;
+  c->h_small[1] = 0;  // the picked series' points (the host entry reads it)
+  if (S == 0) {  // no series: nothing picked (HighestMax.java:45-47)
+    HIP_TRY(hipMemsetAsync(out->series.offsets, 0, sizeof(int64_t), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return OTSDB_OK;
+  }
+  StageTimer tm(c, 13);
+  const int64_t n_out = std::min<int64_t>(ts->topn, S);
+  otsdb_status rc = topn_host_block(c, n_out);
+  if (rc) return rc;
+  TopnWork W;
+  TopnGrid Q;
+  int64_t tiles = 0;
+  if (topn_grid_plan(ts, S, &Q, &tiles)) {
+    if ((rc = topn_number(c, ts, R, res, n_groups, S, W))) return rc;
+    bool missed = false;
+    c->n_topn_grid = 1;
+    rc = topn_grid(c, ts, S, Q, tiles, W, out, &missed);
+    if (rc || !missed) return rc;
+    c->n_topn_miss = 1;
+    out->n_picked = 0;
+    if ((rc = topn_host_block(c, n_out))) return rc;
+  }
+  c->n_topn_general = 1;
+  if ((rc = topn_number(c, ts, R, res, n_groups, S, W))) return rc;
+  return topn_general(c, ts, S, W, out);
+}
+
+}  // namespace
+
+// =========================================================================
 // C-ABI
 // =========================================================================
 extern "C" {
@@ -3515,6 +3937,7 @@ void otsdb_ctx_destroy(otsdb_ctx* c) {
   if (c->h_mdone) hipHostFree(c->h_mdone);
   if (c->h_small) hipHostFree(c->h_small);
   if (c->h_done) hipHostFree(c->h_done);
+  if (c->h_topn) hipHostFree(c->h_topn);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;  // the device buffers free themselves (DevBuf)
 }
@@ -4478,6 +4901,121 @@ otsdb_status otsdb_agg_run_cells(otsdb_ctx* c, const otsdb_query_spec* spec,
   return OTSDB_OK;
 }
 
+otsdb_status otsdb_topn_plan(otsdb_ctx* c, const otsdb_topn_spec* spec,
+                             int32_t n_results, const int64_t* n_groups,
+                             const int64_t* n_points, otsdb_sizes* out) {
+  if (!spec || !out || (n_results > 0 && !n_points))
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  int64_t S = 0, N = 0;
+  std::vector<otsdb_result> shape((size_t)std::max(n_results, 0));
+  for (auto& r : shape) r.offsets = (int64_t*)n_points;  // (non-null: shape only)
+  const otsdb_status rc =
+      check_topn(spec, n_results, shape.data(), n_groups, &S);
+  if (rc) return rc;
+  for (int32_t r = 0; r < n_results; ++r) {
+    if (n_points[r] < 0) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "n_points < 0");
+    N += n_points[r];
+  }
+  out->n_buckets = std::min<int64_t>(spec->topn, S);
+  out->max_out_points = N;
+  // the columnar view (17 B), candidate / sorted / distinct keys (24 B) and
+  // the sort's own scratch (~16 B) a point; ~180 B a series
+  out->workspace_bytes = N * 57 + S * 180 + (1 << 20);
+  return OTSDB_OK;
+}
+
+otsdb_status otsdb_topn_run_device(otsdb_ctx* c, const otsdb_topn_spec* spec,
+                                   int32_t n_results,
+                                   const otsdb_result* results,
+                                   const int64_t* n_groups,
+                                   otsdb_topn_result* out, void* hip_stream) {
+  if (!c || !spec || !out || !out->series.offsets)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  int64_t S = 0;
+  otsdb_status rc = check_topn(spec, n_results, results, n_groups, &S);
+  if (rc) return rc;
+  CtxLock lk(c);
+  HIP_TRY(hipSetDevice(c->device));
+  StreamBinding bind(c, hip_stream);
+  return run_topn_impl(c, spec, n_results, results, n_groups, S, out);
+}
+
+otsdb_status otsdb_topn_run(otsdb_ctx* c, const otsdb_topn_spec* spec,
+                            int32_t n_results, const otsdb_result* results,
+                            const int64_t* n_groups, otsdb_topn_result* out) {
+  if (!c || !spec || !out || !out->series.offsets)
+    return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
+  int64_t S = 0;
+  otsdb_status rc = check_topn(spec, n_results, results, n_groups, &S);
+  if (rc) return rc;
+  CtxLock lk(c);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const int R = n_results;
+  const int64_t n_out = std::min<int64_t>(spec->topn, S);
+  const int64_t cap = std::max<int64_t>(out->series.capacity, 0);
+  std::vector<int64_t> np((size_t)R);
+  for (int r = 0; r < R; ++r) {
+    const int64_t G = n_groups[r];
+    np[r] = G > 0 ? results[r].offsets[G] : 0;
+    if (np[r] < 0 || (np[r] > 0 && (!results[r].ts || !results[r].val ||
+                                     !results[r].is_int)))
+      return fail(OTSDB_E_ILLEGAL_ARGUMENT, "result %d: bad point arrays", r);
+  }
+  // staging layout in HBM: the inputs, then the output
+  std::vector<otsdb_result> dr((size_t)R);
+  otsdb_topn_result dout = *out;
+  auto carve = [&](char* base) {
+    Carve cv{base};
+    for (int r = 0; r < R; ++r) {
+      dr[r].capacity = np[r];
+      dr[r].offsets = cv.take<int64_t>(n_groups[r] + 1);
+      dr[r].ts = cv.take<int64_t>(np[r] + 1);
+      dr[r].val = cv.take<int64_t>(np[r] + 1);
+      dr[r].is_int = cv.take<uint8_t>(np[r] + 1);
+    }
+    dout.series.capacity = cap;
+    dout.series.offsets = cv.take<int64_t>(n_out + 1);
+    dout.series.ts = cv.take<int64_t>(cap + 1);
+    dout.series.val = cv.take<int64_t>(cap + 1);
+    dout.series.is_int = cv.take<uint8_t>(cap + 1);
+    return cv.off + 256;
+  };
+  rc = c->stage.ensure(carve(nullptr));
+  if (rc) return rc;
+  carve((char*)c->stage.p);
+  for (int r = 0; r < R; ++r) {
+    if (n_groups[r] > 0)
+      HIP_TRY(hipMemcpyAsync(dr[r].offsets, results[r].offsets,
+                             8 * (n_groups[r] + 1), hipMemcpyHostToDevice, st));
+    if (np[r] > 0) {
+      HIP_TRY(hipMemcpyAsync(dr[r].ts, results[r].ts, 8 * np[r],
+                             hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(dr[r].val, results[r].val, 8 * np[r],
+                             hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(dr[r].is_int, results[r].is_int, np[r],
+                             hipMemcpyHostToDevice, st));
+    }
+  }
+  rc = run_topn_impl(c, spec, R, dr.data(), n_groups, S, &dout);
+  out->n_picked = dout.n_picked;
+  if (rc && !(rc == OTSDB_E_CAPACITY && c->result_short)) return rc;
+  const int64_t k = out->n_picked;
+  HIP_TRY(hipMemcpyAsync(out->series.offsets, dout.series.offsets, 8 * (k + 1),
+                         hipMemcpyDeviceToHost, st));
+  const int64_t total = rc ? 0 : c->h_small[1];
+  if (total > 0) {
+    HIP_TRY(hipMemcpyAsync(out->series.ts, dout.series.ts, 8 * total,
+                           hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out->series.val, dout.series.val, 8 * total,
+                           hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out->series.is_int, dout.series.is_int, total,
+                           hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  return rc;
+}
+
 otsdb_status otsdb_prof_enable(otsdb_ctx* c, int enable) {
   if (!c) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
   CtxLock lk(c, /*keep_session=*/true);
@@ -4500,12 +5038,12 @@ otsdb_status otsdb_prof_read(otsdb_ctx* c, double* ms, int64_t* launches,
   }
   c->ev_pending.clear();
   c->ev_used = 0;
-  for (int i = 0; i < n && i < 13; ++i) {
+  for (int i = 0; i < n && i < 14; ++i) {
     if (ms) ms[i] = c->prof_ms[i];
     if (launches) launches[i] = c->prof_n[i];
   }
   if (reset)
-    for (int i = 0; i < 13; ++i) {
+    for (int i = 0; i < 14; ++i) {
       c->prof_ms[i] = 0;
       c->prof_n[i] = 0;
     }
@@ -4515,15 +5053,17 @@ otsdb_status otsdb_prof_read(otsdb_ctx* c, double* ms, int64_t* launches,
 otsdb_status otsdb_ctx_counters(otsdb_ctx* c, int64_t* out, int n) {
   if (!c || (n > 0 && !out)) return fail(OTSDB_E_ILLEGAL_ARGUMENT, "null");
   CtxLock lk(c, /*keep_session=*/true);
-  const int64_t v[18] = {c->n_cells_uniform, c->n_cells_general,
+  const int64_t v[21] = {c->n_cells_uniform, c->n_cells_general,
                          c->n_cells_uni_miss, c->sel.key_reads, c->sel.passes,
                          c->n_multi_ds,       c->n_multi_group, c->n_multi_kt,
                          c->n_multi_tf,       c->sel.sessions,
                          c->n_panel_passes,   c->n_panel_mats,
                          c->n_multi_fold,     c->n_hist_fold,
                          c->n_hist_pct,       c->n_hr_decoded,
-                         c->n_hr_skipped,     c->n_hr_dropped};
-  for (int i = 0; i < n && i < 18; ++i) out[i] = v[i];
+                         c->n_hr_skipped,     c->n_hr_dropped,
+                         c->n_topn_grid,      c->n_topn_general,
+                         c->n_topn_miss};
+  for (int i = 0; i < n && i < 21; ++i) out[i] = v[i];
   return OTSDB_OK;
 }
 

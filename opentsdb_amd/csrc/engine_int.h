@@ -136,8 +136,8 @@ struct otsdb_ctx {
   std::vector<hipEvent_t> ev_pool;
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev_pending;
   size_t ev_used = 0;
-  double prof_ms[13] = {0};
-  int64_t prof_n[13] = {0};
+  double prof_ms[14] = {0};
+  int64_t prof_n[14] = {0};
   DevBuf cells_ws;   // cells query: series row / point offsets
   DevBuf cells_col;  // cells query fallback: decoded columns
   DevBuf cal;        // calendar bucket edges of the current query
@@ -188,6 +188,14 @@ struct otsdb_ctx {
   // decoded into points, cells skipped as undecodable, points dropped by a
   // same-key merge
   int64_t n_hr_decoded = 0, n_hr_skipped = 0, n_hr_dropped = 0;
+  // otsdb_ctx_counters [18..20], of the last otsdb_topn_* call: runs of the
+  // grid path, of the general path, grid promises missed (re-run general)
+  int64_t n_topn_grid = 0, n_topn_general = 0, n_topn_miss = 0;
+  // what a top-N call reports through: mapped host memory the last kernels
+  // write {error word, total, n_picked, flags}, picked and key into
+  int64_t* h_topn = nullptr;
+  int64_t* d_topn = nullptr;
+  size_t topn_host_cap = 0;
   // cross-rank selection session (otsdb_sel_*): lives in `ws` between calls
   struct {
     bool active = false;

@@ -478,6 +478,47 @@ class Engine:
                            None if cnt is None else cnt[offs[g]:offs[g + 1]])
                 for g in range(G)]
 
+    def topn_counters(self):
+        """Of the last top-N call (otsdb_ctx_counters [18..20]): runs of the
+        grid path, runs of the general path, grid promises missed (the
+        general path then ran again)."""
+        out = self._counters(21)
+        return dict(grid=int(out[18]), general=int(out[19]),
+                    grid_miss=int(out[20]))
+
+    def run_topn(self, function, topn, start_ms, end_ms, results,
+                 grid_interval_ms=0):
+        """highestMax / highestCurrent (host arrays): `results` is a list of
+        what run() returns, one list of DataPoints per sub-query; `function`
+        a gexp name ("highestMax", "highestCurrent"), `topn` an int or the
+        function's parameter string; start_ms / end_ms the TSQuery's bounds;
+        grid_interval_ms core.topn_grid_interval_ms of the queries'
+        downsampler (0: no promise).  Returns (picked, keys, series): the
+        picked series' numbers in the inputs' flat order (empty series
+        counted), their keys (float64, NaN canonical) and their whole point
+        lists as DataPoints, in rank order."""
+        ts = topn_spec(function, topn, start_ms, end_ms, grid_interval_ms)
+        rs, ng, keep, S, N = _topn_host_inputs(results)
+        n_out = min(ts.topn, S)
+        cap = max(N, 1)
+        offs = np.zeros(n_out + 1, np.int64)
+        ots = np.zeros(cap, np.int64)
+        bits = np.zeros(cap, np.int64)
+        isint = np.zeros(cap, np.uint8)
+        picked = np.zeros(max(n_out, 1), np.int64)
+        key = np.zeros(max(n_out, 1), np.int64)
+        out = abi.TopNResult(
+            abi.Result(cap, offs.ctypes.data, ots.ctypes.data,
+                       bits.ctypes.data, isint.ctypes.data),
+            picked.ctypes.data, key.ctypes.data, 0)
+        self._check(self.lib.otsdb_topn_run(
+            self.ctx, C.byref(ts), len(results), rs, ng.ctypes.data,
+            C.byref(out)))
+        k = int(out.n_picked)
+        return (picked[:k].copy(), key[:k].view(np.float64).copy(),
+                [DataPoints(ots[offs[i]:offs[i + 1]], bits[offs[i]:offs[i + 1]],
+                            isint[offs[i]:offs[i + 1]]) for i in range(k)])
+
     def plan_multi(self, spec, aggs, batch, interps=None):
         n, ids, it = multi_args(aggs, interps)
         sz = abi.Sizes()
@@ -531,6 +572,116 @@ class Engine:
             self.ctx, C.byref(spec), n, ds.ctypes.data, ids.ctypes.data,
             it.ctypes.data, C.byref(b), rs))
         return points()
+
+
+def topn_spec(function, topn, start_ms, end_ms, grid_interval_ms=0):
+    """The otsdb_topn_spec of a highestMax / highestCurrent call, checked as
+    the reference checks it before anything touches the device: `function` a
+    gexp name or id (core.topn_function), `topn` an int or the function's
+    parameter string (core.parse_topn)."""
+    from .core import parse_topn, topn_function
+    fn = topn_function(function)
+    if isinstance(topn, str):
+        topn = parse_topn([topn])
+    topn = int(topn)
+    if topn < 1:
+        raise IllegalArgumentException(
+            "Top n value must be greater than zero: %d" % topn)
+    if topn > 2 ** 31 - 1:
+        raise IllegalArgumentException("Invalid parameter, must be an integer")
+    if int(start_ms) < 0:
+        raise IllegalArgumentException("negative start")
+    if int(grid_interval_ms) < 0:
+        raise IllegalArgumentException("negative grid interval")
+    return abi.TopNSpec(fn, topn, int(start_ms), int(end_ms),
+                        int(grid_interval_ms))
+
+
+def _topn_host_inputs(results):
+    """The sub-query results of Engine.run_topn (each a list of DataPoints)
+    as host otsdb_result structs: (abi.Result array, int64 group counts, the
+    arrays kept alive, total series, total points)."""
+    R = len(results)
+    rs = (abi.Result * max(R, 1))()
+    ng = np.zeros(max(R, 1), np.int64)
+    keep = []
+    S = N = 0
+    for r, groups in enumerate(results):
+        groups = list(groups)
+        offs = np.zeros(len(groups) + 1, np.int64)
+        for g, d in enumerate(groups):
+            offs[g + 1] = offs[g] + len(d.ts)
+        cat = lambda xs, dt: (np.ascontiguousarray(np.concatenate(xs), dt)  # noqa: E731
+                              if xs else np.zeros(0, dt))
+        ts = cat([np.asarray(d.ts, np.int64) for d in groups], np.int64)
+        bits = cat([np.asarray(d.bits, np.int64) for d in groups], np.int64)
+        isint = cat([np.asarray(d.is_int, np.uint8) for d in groups], np.uint8)
+        # (never a null array: an empty result still passes real pointers)
+        pad = lambda a: a if len(a) else np.zeros(1, a.dtype)  # noqa: E731
+        ts, bits, isint = pad(ts), pad(bits), pad(isint)
+        keep.append((offs, ts, bits, isint))
+        rs[r] = abi.Result(int(offs[-1]), offs.ctypes.data, ts.ctypes.data,
+                           bits.ctypes.data, isint.ctypes.data)
+        ng[r] = len(groups)
+        S += len(groups)
+        N += int(offs[-1])
+    return rs, ng, keep, S, N
+
+
+class DeviceTopN:
+    """otsdb_topn_result for the device entry: the picked series in HBM
+    (offsets [n_out + 1], ts / val / is_int [cap]) and the host arrays picked
+    / key [n_out]; n_picked after the call."""
+
+    def __init__(self, torch, n_out, cap, device):
+        n_out, cap = max(int(n_out), 0), max(int(cap), 0)
+        self.cap = cap
+        self.offsets = torch.zeros(n_out + 1, dtype=torch.int64, device=device)
+        self.ts = torch.zeros(max(cap, 1), dtype=torch.int64, device=device)
+        self.val = torch.zeros(max(cap, 1), dtype=torch.int64, device=device)
+        self.is_int = torch.zeros(max(cap, 1), dtype=torch.uint8, device=device)
+        self.picked = np.zeros(max(n_out, 1), np.int64)
+        self.key = np.zeros(max(n_out, 1), np.int64)
+        self.n_picked = 0
+
+    def as_abi(self):
+        return abi.TopNResult(
+            abi.Result(self.cap, self.offsets.data_ptr(), self.ts.data_ptr(),
+                       self.val.data_ptr(), self.is_int.data_ptr()),
+            self.picked.ctypes.data, self.key.ctypes.data, 0)
+
+    def points(self):
+        """The picked series as host DataPoints, in rank order."""
+        k = self.n_picked
+        offs = self.offsets[:k + 1].cpu().numpy()
+        n = int(offs[-1]) if k else 0
+        ts, bits = self.ts[:n].cpu().numpy(), self.val[:n].cpu().numpy()
+        isint = self.is_int[:n].cpu().numpy()
+        return [DataPoints(ts[offs[i]:offs[i + 1]], bits[offs[i]:offs[i + 1]],
+                           isint[offs[i]:offs[i + 1]]) for i in range(k)]
+
+
+def run_topn_device(engine, function, topn, start_ms, end_ms, dresults, dtop,
+                    stream=None, grid_interval_ms=0):
+    """Device-resident highestMax / highestCurrent: `dresults` is a list of
+    DeviceResults as run_device and its kin filled them (one per sub-query),
+    `dtop` a DeviceTopN.  The picked series stay in HBM; dtop.picked /
+    dtop.key / dtop.n_picked are on the host when the call returns.  A
+    DeviceTopN too small raises CapacityException with dtop.n_picked and
+    dtop.offsets whole (offsets[n_picked] is the capacity a retry needs)."""
+    ts = topn_spec(function, topn, start_ms, end_ms, grid_interval_ms)
+    R = len(dresults)
+    rs = (abi.Result * max(R, 1))()
+    ng = np.zeros(max(R, 1), np.int64)
+    for r, d in enumerate(dresults):
+        rs[r] = d.as_abi()
+        ng[r] = d.offsets.numel() - 1
+    out = dtop.as_abi()
+    st = engine.lib.otsdb_topn_run_device(
+        engine.ctx, C.byref(ts), R, rs, ng.ctypes.data, C.byref(out),
+        _stream(stream))
+    dtop.n_picked = int(out.n_picked)
+    engine._check(st)
 
 
 class HistPoints:
